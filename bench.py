@@ -8,10 +8,19 @@ noise: Philox. The metric's N = 256 candidates per round are split over the GPUs
 scaling, N_local = 256 / n_gpus); --n-per-gpu N runs N per GPU instead (weak scaling), and a
 multi-GPU run also reports the N = 256-per-GPU weak-scaling rate as a side field.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--n N | --n-per-gpu N] [--no-extras]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--n N | --n-per-gpu N] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...      (driver, N > 1)
 
-Rank 0 prints ONE JSON line. Extra fields (single-GPU runs):
+Rank 0 prints ONE JSON line. A plain run does only what the headline needs: set-up, W warm-up rounds,
+K timed rounds, the line (`ms_per_step` = milliseconds per timed round). --dump-outputs DIR also writes
+what the last timed round returned to its caller (search.RoundResult) as DIR/<name>.npy: scores (fp64,
+all candidates), best ([best_index, best_score], fp64) and images (fp32, this rank's denoised
+candidates; above 48 MB a fixed seeded sample of them, with their indices in images_index). The
+inputs are functions of the arguments alone (seeded weights, Philox noise of (seed, round, index)),
+so two builds can be compared output for output.
+
+Everything else needs --full (with it, --no-extras / --no-cpu-baseline / --no-live-traffic /
+--no-weak-line switch single parts off again). Extra fields of a --full run (single-GPU runs):
   roofline      the dominant kernel (fused GroupNorm conv) in steady state with HIP events on
                 the UNet's stream, its PMC HBM traffic (profiles/, this commit), the conv tiles'
                 HBM GB/s, and the attention kernels' MFMA utilisation;
@@ -305,11 +314,36 @@ def leg(name, make_net, n: int, img: int, T: int, window: int, cfg: bool, precis
     return out
 
 
+DUMP_IMAGE_BYTES = 48 << 20  # --dump-outputs: cap of images.npy (the whole dump stays under 64 MB)
+
+
+def dump_outputs(d: str, r) -> None:
+    """--dump-outputs: the RoundResult of the last timed round as d/<name>.npy (fp64 scores and
+    best, fp32 images; more images than DUMP_IMAGE_BYTES hold: a fixed seeded sample of them)."""
+    import numpy as np
+
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "scores.npy"), r.scores.double().numpy())
+    np.save(os.path.join(d, "best.npy"), np.array([r.best_index, r.best_score], dtype=np.float64))
+    img = r.local_images
+    keep = max(1, DUMP_IMAGE_BYTES // (4 * img[0].numel()))
+    if img.shape[0] > keep:
+        idx = np.sort(np.random.default_rng(0).choice(img.shape[0], keep, replace=False))
+        np.save(os.path.join(d, "images_index.npy"), idx.astype(np.float64))
+        img = img[torch.from_numpy(idx).to(img.device)]
+    np.save(os.path.join(d, "images.npy"), img.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2)
+    ap.add_argument("--steps", type=int, default=2, help="timed rounds")
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed round returned (scores, best, images) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline census, PMC traffic, calibration, N sweep, fp32, the other configs, "
+                         "the CPU baseline and (N > 1) the weak-scaling field; a plain run times the headline only")
     ap.add_argument("--n", "--n-total", dest="n_total", type=int, default=256,
                     help="global N of the metric (N=256), split over the GPUs: strong scaling (default)")
     ap.add_argument("--n-per-gpu", type=int, default=0, help="weak scaling instead: N per GPU")
@@ -323,6 +357,8 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-weak-line", action="store_true", help="(N > 1) skip the N=256-per-GPU weak-scaling field")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -377,11 +413,13 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, r)
 
     # N > 1 with the metric's fixed N = 256: also the weak-scaling rate (N = 256 per GPU, the same
     # round protocol over the same ranks) as a side field; the headline stays the metric's N
     weak = None
-    if world > 1 and scaling == "strong" and not args.no_weak_line:
+    if args.full and world > 1 and scaling == "strong" and not args.no_weak_line:
         nw = 256 * world
         net.reserve(256)
         eng.run_round(20_000, nw, shape)  # capture the N_local = 256 graph
@@ -399,7 +437,7 @@ def main():
                 "ms_per_step": round(float(tw.item()) / args.steps * 1e3, 2)}
 
     roof = None
-    if rank == 0:
+    if args.full and rank == 0:
         progress(f"headline: {n_total * args.steps / dt:.3f} candidate-images/s; roofline census")
         ops, agg, nat, x, t = census(net, n_local, 32)
         kernel, roof = dominant_roofline(ops, agg, nat, x, t, args.precision)
@@ -502,7 +540,7 @@ def main():
                 roof["attention"]["unfused"] = att["attn"]
 
     extras = {}
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         # north_star N sweep on the same path (headline N is the main line)
         sweep = {}
         for n, window in ((8, 1000), (16, 1000), (32, 1000), (64, 1000), (128, 1000), (256, 1000), (1024, 100)):
@@ -543,7 +581,7 @@ def main():
         }
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         progress("cpu baseline")
         cpu = cpu_baseline(args.T, seconds=args.cpu_seconds)
 

@@ -68,6 +68,35 @@ def test_cpu_baseline_conversion_check_fields():
     assert abs(c["deviation"] - dev) < 5e-3 and c["agrees"] == (abs(c["deviation"]) <= 0.15)
 
 
+def test_dump_outputs_writes_the_round_result(tmp_path, monkeypatch):
+    """--dump-outputs: scores / best in fp64 and the images in fp32, whole when they fit the cap, else
+    the same seeded sample of candidates every time, with their indices beside them."""
+    import numpy as np
+    import torch
+    from itsd.search import RoundResult
+
+    b = _bench()
+    g = torch.Generator().manual_seed(3)
+    img = torch.randn(10, 3, 4, 4, generator=g)
+    sc = torch.randn(10, generator=g, dtype=torch.float64)
+    r = RoundResult(scores=sc, best_index=int(sc.argmax()), best_score=float(sc.max()), local_images=img)
+    b.dump_outputs(str(tmp_path / "a"), r)
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert sorted(got) == ["best", "images", "scores"]
+    assert got["scores"].dtype == np.float64 and np.array_equal(got["scores"], sc.numpy())
+    assert got["best"].dtype == np.float64 and got["best"].tolist() == [r.best_index, r.best_score]
+    assert got["images"].dtype == np.float32 and np.array_equal(got["images"], img.numpy())
+    # a cap that holds 4 of the 10 images: a sorted sample without repeats, the same in both dumps
+    monkeypatch.setattr(b, "DUMP_IMAGE_BYTES", 4 * img[0].numel() * 4)
+    for d in ("b", "c"):
+        b.dump_outputs(str(tmp_path / d), r)
+    idx = np.load(tmp_path / "b" / "images_index.npy")
+    assert idx.shape == (4,) and len(set(idx.tolist())) == 4 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(idx, np.load(tmp_path / "c" / "images_index.npy"))
+    assert np.array_equal(np.load(tmp_path / "b" / "images.npy"), img.numpy()[idx.astype(np.int64)])
+    assert np.array_equal(np.load(tmp_path / "b" / "scores.npy"), sc.numpy())
+
+
 def test_conv_alg_bytes_counts_every_operand_once():
     """the algorithmic bytes of a fused conv launch count the residual operand and the
     GroupNorm statistics slabs (output written, fused input read), besides input, weights and output."""

@@ -12,7 +12,7 @@
 #   census=N[:arch]           tools/census.py per-launch census of one forward (arch a / c; c: N is the guided batch)
 #   timeline=N:op,op,...      tools/timeline.py p5 launch timelines (stamps build ab_libs/libitsd_hip_stamps.so)
 #   pmc=N                     PMC passes over one census forward + per-dispatch table + traffic files
-#   bench                     python bench.py (the driver's line, all extras)
+#   bench                     python bench.py --full (the driver's line, all extras)
 #   prof                      rocprofv3 --kernel-trace --stats of the bench command (no extras)
 set -o pipefail
 tag=$1; shift
@@ -47,12 +47,12 @@ for step in "$@"; do
       timeout -k 10 900 bash tools/pmc_passes.sh "$out/pmc" --n "${arg:-256}" > "$out/pmc.log" 2>&1 || fail pmc $? "$out/pmc.log"
       python tools/pmc_dispatch.py "$out/pmc" > "$out/pmc_dispatch_table.txt" || echo dispatch_table_fail ;;
     bench)
-      timeout -k 10 900 python bench.py > "$out/bench.json" 2> "$out/bench.err" || fail bench $? "$out/bench.err"
+      timeout -k 10 900 python bench.py --full > "$out/bench.json" 2> "$out/bench.err" || fail bench $? "$out/bench.err"
       tail -c 400 "$out/bench.json" ;;
     prof)
       ( cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" &&
         timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/prof" -o bench -- \
-          python3 bench.py --no-extras --no-cpu-baseline --no-live-traffic > "$out/prof_bench.json" 2> "$out/prof.err" ) || fail prof $? "$out/prof.err"
+          python3 bench.py --full --no-extras --no-cpu-baseline --no-live-traffic > "$out/prof_bench.json" 2> "$out/prof.err" ) || fail prof $? "$out/prof.err"
       find "$out/prof" -name "*kernel_trace.csv" -delete
       find "$out/prof" -name "*stats.csv" ;;
     *) echo "unknown step $name"; exit 2 ;;
