@@ -177,15 +177,16 @@ int itsd_profile_ops(itsd_unet* u, const float* x, const int32_t* t, int n, int 
 int itsd_profile_op(itsd_unet* u, const float* x, const int32_t* t, int n, int op_index, int reps, double* ms,
                     void* stream);
 
-/* Process-wide choices between the shipped paths (api.hip lists every key and its range): kernel and tile
- * choices ("conv_variant", "splitk" 0/1, "splitk_inl", "small_conv", "gn_wide", "fuse_gn", "io_mfma", "p4_w",
- * "p4_sub", "p4_plain", "p4_c96", "p5", "p5_split", "p5_sc", "p5_pub", "p5_dist", "p5_xl", "gn_fold", "attn_split", "attn_wide",
- * "attn_wide_nq", "conv1x1" 0/1, "small_wide", "small_8x8", "subpix_split", "convt_prune"), the in-kernel hand-off
- * poll bound ("spin_bound"), and build-time choices read at create ("attn_fuse", "attn_s1", "tap_prune",
- * "down_merge"). Defaults are the shipped choices; every alternative is covered by a parity test. Measurement
- * switches of measured-and-dropped variants ("conv_dbg", "attn_cs", "attn_aq", "p4_xcd", "small_minks", forced
- * "splitk" slice counts, "conv1x1" 2) exist in diagnostic builds only (tools/build_diag.sh): this library returns
- * ITSD_ERR_INVALID for them. */
+/* Process-wide choices between the shipped paths (api.hip's kOptions table is the list: every key with its range
+ * and meaning): kernel and tile choices ("conv_variant", "splitk" 0/1, "splitk_inl", "subpix_split", "conv1x1" 0/1,
+ * "small_conv", "small_8x8", "small_wide", "small_gn", "gn_wide", "gn_fold", "p4_w", "p4_c96", "p4_sub", "p4_plain",
+ * "p5", "p5_split", "p5_sc", "p5_pub", "p5_xl", "p5_dist", "convt_prune", "attn_split", "attn_wide",
+ * "attn_wide_nq"), the in-kernel hand-off poll bound ("spin_bound"), and build-time choices read at create
+ * ("fuse_gn", "io_mfma", "attn_fuse", "attn_s1", "tap_prune", "down_merge"). Defaults are the shipped choices; every
+ * alternative is covered by a parity test. Measurement switches of measured-and-dropped variants ("conv_dbg",
+ * "attn_cs", "attn_aq", "p4_xcd", "small_minks", "p5_c64", forced "splitk" slice counts, "conv1x1" 2) exist in
+ * diagnostic builds only (tools/build_diag.sh): this library returns ITSD_ERR_INVALID for them. A refused call
+ * leaves the previous value in place. */
 int itsd_set_option(const char* key, int value);
 
 /* Introspection of a handle (no device work): "graph_captures" (step graphs captured and

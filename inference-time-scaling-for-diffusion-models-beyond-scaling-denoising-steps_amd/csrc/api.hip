@@ -24,7 +24,7 @@
 #include "itsd.h"
 
 namespace itsd {
-template <typename T> hipError_t launch_conv(const ConvArgs&, hipStream_t);
+template <typename T> hipError_t launch_conv(const ConvArgs&, const ConvPlan&, hipStream_t);
 template <typename T> hipError_t launch_groupnorm(const GNArgs&, int, hipStream_t);
 template <typename T> hipError_t launch_attn(const AttnArgs&, int, hipStream_t);
 bool attn_flash_ok(int S, int C);
@@ -45,13 +45,8 @@ hipError_t launch_add_int(int*, int, hipStream_t);
 int calibrate_run(int what, double* value, hipStream_t s);
 hipError_t launch_run_begin(int*, int, int*, RunParams*, const RunParams&, hipStream_t);
 int g_option_gen = 0;  // bumped by every itsd_set_option: part of the step-graph cache key
-bool conv_gn_eligible(int H, int W);
+bool conv_gn_eligible(int H, int W);  // (shape-only: the op builder's; every per-launch choice is plan_conv's, common.h)
 bool p5_eligible(int H, int W);
-bool conv_p5_selected(const ConvArgs& a);
-bool conv_p4_selected(const ConvArgs& a);
-bool conv_p5_sc_fold(const ConvArgs& a);
-int conv_small_split(const ConvArgs& a);
-int conv_gn_wide_segs(int H, int W, int M, int Cout, bool any_tiles = false);
 hipError_t launch_gn_coef(const GNArgs&, int, float*, hipStream_t);
 hipError_t launch_head_mfma(const HeadArgs&, hipStream_t);
 hipError_t launch_tail_mfma(const TailArgs&, hipStream_t);
@@ -113,8 +108,8 @@ struct Act {
 enum OpKind { OP_GN, OP_CONV, OP_ATTN, OP_GNCOEF, OP_ATTNBLOCK };
 constexpr int kCensusAttnBlock = 7;  // census kind of OP_ATTNBLOCK (runtime.py "attnblock")
 constexpr int kCensusConvGN = 4;  // census kind of a fused GroupNorm+SiLU conv (conv3x3_gn_kernel)
-constexpr int kCensusConvGNW = 5;   // ... run as conv3x3_gn_wide_kernel<1>
-constexpr int kCensusConvGNW4 = 6;  // ... run as conv3x3_gn_wide_kernel<4>
+constexpr int kCensusConvGNW = 5;   // ... whose shape has 256-pixel tiles of one image's rows (ConvPlan::wide_segs 1)
+constexpr int kCensusConvGNW4 = 6;  // ... of four 8x8 images (wide_segs 4)
 
 struct Op {
   OpKind kind;
@@ -490,7 +485,7 @@ struct Builder {
       u->ops.back().gn_gamma = u->ops[u->ops.size() - 2].gamma;
       u->ops.back().gn_beta = u->ops[u->ops.size() - 2].beta;
     }
-    // (plain 3x3 stride-1 convs too: conv3x3_gn_p4_kernel's plain form, conv_p4_plain_selected)
+    // (plain 3x3 stride-1 convs too: conv3x3_gn_p4_kernel's plain form, plan_conv's P4_PLAIN)
     const bool plain3 = coef == SIZE_MAX && ks == 3 && stride == 1 && pad == 1 && !ups && Cout % 128 == 0 &&
                         Cin % 128 == 0 && Hout == Wout && (Hout == 32 || Hout == 16 || Hout == 8);
     if ((coef != SIZE_MAX || plain3) && u->bf16 && Cout % 32 == 0 && (ks * ks * Cin) % 16 == 0)
@@ -897,8 +892,9 @@ struct RunCtx {
   std::vector<int>* ev_op = nullptr;   // program op index (1-based; 0 = head / tail) of each launch
 };
 
-// The launch arguments of a conv op (shared by launch_op and run_program's gn_fold decision).
-int conv_args(itsd_unet* u, const Op& o, const RunCtx& c, ConvArgs& a) {
+// The launch arguments and the launch plan of a conv op (resolve_program calls it once per op and pass). Every failure
+// returns before a fold is set: a failed op's arguments fold nothing.
+int conv_args(itsd_unet* u, const Op& o, const RunCtx& c, ConvArgs& a, ConvPlan& p) {
     const Act& in = u->acts[o.src1];
     const Act& out = u->acts[o.dst];
     a.src1 = u->ap(o.src1);
@@ -961,12 +957,32 @@ int conv_args(itsd_unet* u, const Op& o, const RunCtx& c, ConvArgs& a) {
       if (a.C1 % epc || a.C2 % epc || a.Cout % 4 || a.K % epc)
         return fail(ITSD_ERR_INVALID, "conv channels must be multiples of " + std::to_string(epc));
     }
+  // The launch plan, made once here: launch_conv runs it, and the three folds below are read off it (none of the
+  // fields they set enters the plan). A block2 conv offers its ResBlock's 1x1 shortcut as a candidate.
+  if (o.sc_op >= 0 && itsd::g_p5_sc) {
+    const Op& sc = u->ops[o.sc_op];
+    a.sc_src1 = u->ap(sc.src1);
+    a.sc_src2 = sc.src2 >= 0 ? u->ap(sc.src2) : nullptr;
+    a.sc_C1 = u->acts[sc.src1].C;
+    a.sc_C2 = sc.src2 >= 0 ? u->acts[sc.src2].C : 0;
+    a.sc_wfrag = u->wdev + o.sc_wfrag;
+  }
+  p = plan_conv(a, u->bf16);
+  const bool p5 = p.kernel == ConvKernel::P5 || p.kernel == ConvKernel::P5_SHARED;
+  const bool p4 = p.kernel == ConvKernel::P4_GN || p.kernel == ConvKernel::P4_C96;
+  if (p.sc_split) {  // the shortcut folded in as K slices (run_program then skips the shortcut's launch)
+    a.bias = u->wp(o.bias_sc);
+    a.resid = nullptr;
+  } else {
+    a.sc_src1 = a.sc_src2 = a.sc_wfrag = nullptr;
+    a.sc_C1 = a.sc_C2 = 0;
+  }
   // gn_fold: conv3x3_gn_p5_kernel / conv3x3_gn_p4_kernel reduce the input's statistics slabs themselves
   // (run_program then skips the op's gn_coef launch); up to 8 slots an image (32x32): the 32 slots of a
   // 64x64 image made the in-kernel reduction 4-12 dependent load batches (measured: the 64x64 level
   // 0.90 ms folded vs 0.55 ms with its gn_coef launches, C4 at N = 16)
   if (a.gn_coef && o.gn_gamma != SIZE_MAX && itsd::g_gn_fold && (a.C1 + a.C2) % 128 == 0 && in.H * in.W <= 1024 &&
-      (conv_p5_selected(a) || conv_p4_selected(a))) {
+      (p5 || p4)) {
     a.gn_fold = 1;
     a.gn_st1 = (const float*)(u->ws + u->acts[o.src1].stats);
     a.gn_st2 = o.src2 >= 0 ? (const float*)(u->ws + u->acts[o.src2].stats) : nullptr;
@@ -980,8 +996,8 @@ int conv_args(itsd_unet* u, const Op& o, const RunCtx& c, ConvArgs& a) {
   // channels inside one 64-cout tile
   if (o.gn_next >= 0 && itsd::g_small_gn && u->bf16 && a.stats && !a.gn_coef && !o.subpix && !a.vt_out &&
       u->acts[o.dst].spi == 0) {
-    const int HWo = a.Hout * a.Wout, gs = a.Cout / 32;
-    if (HWo <= 16 && 64 % HWo == 0 && a.Cout % 64 == 0 && gs >= 2 && 64 % gs == 0 && conv_small_split(a)) {
+    const int HWo = a.Hout * a.Wout, gs = a.Cout / kGnGroups;
+    if (HWo <= 16 && 64 % HWo == 0 && a.Cout % 64 == 0 && gs >= 2 && 64 % gs == 0 && p.kernel == ConvKernel::SMALL) {
       const Op& g = u->ops[o.gn_next];
       a.gn_out = u->ap(g.dst);
       a.go_gamma = u->wp(g.gamma);
@@ -989,24 +1005,31 @@ int conv_args(itsd_unet* u, const Op& o, const RunCtx& c, ConvArgs& a) {
       a.go_silu = g.silu;
     }
   }
-  if (o.sc_op >= 0 && itsd::g_p5_sc) {  // the shortcut folded in (run_program then skips the shortcut's launch)
-    const Op& sc = u->ops[o.sc_op];
-    ConvArgs t = a;
-    t.sc_src1 = u->ap(sc.src1);
-    t.sc_src2 = sc.src2 >= 0 ? u->ap(sc.src2) : nullptr;
-    t.sc_C1 = u->acts[sc.src1].C;
-    t.sc_C2 = sc.src2 >= 0 ? u->acts[sc.src2].C : 0;
-    t.sc_wfrag = u->wdev + o.sc_wfrag;
-    if (conv_p5_sc_fold(t)) {
-      a = t;
-      a.bias = u->wp(o.bias_sc);
-      a.resid = nullptr;
-    }
-  }
   return ITSD_OK;
 }
 
-int launch_op(itsd_unet* u, const Op& o, const RunCtx& c, hipStream_t s) {
+// A conv op resolved for one pass: its launch arguments, its plan, and conv_args' status (with its message) for when
+// the op's turn comes. Non-conv ops keep the empty entry.
+struct ConvLaunch {
+  ConvArgs a{};
+  ConvPlan p;
+  int rc = ITSD_OK;
+  std::string err;
+};
+
+// Every conv op of the program resolved once (indexed as u->ops): what run_program launches, skips and reports.
+std::vector<ConvLaunch> resolve_program(itsd_unet* u, const RunCtx& c) {
+  std::vector<ConvLaunch> r(u->ops.size());
+  for (size_t oi = 0; oi < u->ops.size(); ++oi) {
+    if (u->ops[oi].kind != OP_CONV) continue;
+    r[oi].rc = conv_args(u, u->ops[oi], c, r[oi].a, r[oi].p);
+    if (r[oi].rc != ITSD_OK) r[oi].err = g_err;
+  }
+  return r;
+}
+
+// cl: the op's resolved entry (conv ops)
+int launch_op(itsd_unet* u, const Op& o, const RunCtx& c, const ConvLaunch* cl, hipStream_t s) {
   hipError_t e = hipSuccess;
   if (o.kind == OP_GNCOEF) {
     GNArgs g{};
@@ -1015,7 +1038,7 @@ int launch_op(itsd_unet* u, const Op& o, const RunCtx& c, hipStream_t s) {
     g.HW = u->acts[o.src1].H * u->acts[o.src1].W;
     g.gamma = u->wp(o.gamma);
     g.beta = u->wp(o.beta);
-    g.eps = 1e-5f;
+    g.eps = kGnEps;
     g.st1 = (const float*)(u->ws + u->acts[o.src1].stats);
     g.st2 = o.src2 >= 0 ? (const float*)(u->ws + u->acts[o.src2].stats) : nullptr;
     g.spi1 = u->acts[o.src1].spi;
@@ -1030,7 +1053,7 @@ int launch_op(itsd_unet* u, const Op& o, const RunCtx& c, hipStream_t s) {
     a.HW = u->acts[o.src1].H * u->acts[o.src1].W;
     a.gamma = u->wp(o.gamma);
     a.beta = u->wp(o.beta);
-    a.eps = 1e-5f;
+    a.eps = kGnEps;
     a.silu = o.silu;
     a.dst = u->ap(o.dst);
     a.st1 = (const float*)(u->ws + u->acts[o.src1].stats);
@@ -1039,9 +1062,8 @@ int launch_op(itsd_unet* u, const Op& o, const RunCtx& c, hipStream_t s) {
     a.spi2 = o.src2 >= 0 ? u->acts[o.src2].spi : 0;
     e = u->bf16 ? launch_groupnorm<bf16_t>(a, c.nb, s) : launch_groupnorm<float>(a, c.nb, s);
   } else if (o.kind == OP_CONV) {
-    ConvArgs a{};
-    CHK(conv_args(u, o, c, a));
-    e = u->bf16 ? launch_conv<bf16_t>(a, s) : launch_conv<float>(a, s);
+    if (cl->rc != ITSD_OK) return fail(cl->rc, cl->err);
+    e = u->bf16 ? launch_conv<bf16_t>(cl->a, cl->p, s) : launch_conv<float>(cl->a, cl->p, s);
   } else if (o.kind == OP_ATTNBLOCK) {
     AttnBlockArgs a{};
     const Act& in = u->acts[o.src1];
@@ -1096,7 +1118,8 @@ double op_flops(const itsd_unet* u, const Op& o, int nb) {
   return 0.0;
 }
 
-int run_program(itsd_unet* u, const RunCtx& c, hipStream_t s) {
+// rp: resolve_program's entries for this pass
+int run_program(itsd_unet* u, const RunCtx& c, const std::vector<ConvLaunch>& rp, hipStream_t s) {
   int cur_op = 0;  // program op being launched (census: 1-based, 0 head / tail)
   auto mark = [&](int kind, double fl, const std::function<int()>& fn) -> int {
     if (!c.census) return fn();
@@ -1136,31 +1159,22 @@ int run_program(itsd_unet* u, const RunCtx& c, hipStream_t s) {
   // census kinds: OpKind, and kCensusConvGN for the fused GroupNorm+SiLU convs
   for (size_t oi = 0; oi < u->ops.size(); ++oi) {
     const Op& o = u->ops[oi];
-    if (o.kind == OP_GNCOEF && oi + 1 < u->ops.size() && u->ops[oi + 1].kind == OP_CONV) {
-      ConvArgs na{};  // gn_fold: the consumer conv finalizes this GroupNorm itself
-      if (conv_args(u, u->ops[oi + 1], c, na) == ITSD_OK && na.gn_fold) continue;
-    }
-    if (o.kind == OP_GN && o.gn_from >= 0) {
-      ConvArgs na{};  // a GroupNorm its producer conv wrote in its epilogue
-      if (conv_args(u, u->ops[o.gn_from], c, na) == ITSD_OK && na.gn_out) continue;
-    }
-    if (o.kind == OP_CONV && o.sc_into >= 0) {
-      ConvArgs na{};  // a shortcut its block2 conv runs as K slices
-      if (conv_args(u, u->ops[o.sc_into], c, na) == ITSD_OK && na.sc_C1 + na.sc_C2 > 0) continue;
-    }
+    // launches folded into a neighbouring conv's (a conv whose conv_args failed folds nothing and fails at its turn):
+    // gn_fold: the consumer conv finalizes this GroupNorm itself
+    if (o.kind == OP_GNCOEF && oi + 1 < u->ops.size() && rp[oi + 1].a.gn_fold) continue;
+    // a GroupNorm its producer conv wrote in its epilogue
+    if (o.kind == OP_GN && o.gn_from >= 0 && rp[o.gn_from].a.gn_out) continue;
+    // a shortcut its block2 conv runs as K slices
+    if (o.kind == OP_CONV && o.sc_into >= 0 && rp[o.sc_into].p.sc_split) continue;
+    const ConvLaunch& cl = rp[oi];
     int kind = o.kind == OP_ATTNBLOCK ? kCensusAttnBlock : (int)o.kind;
     cur_op = (int)oi + 1;
-    if (o.kind == OP_CONV && o.coef != SIZE_MAX) {
-      const Act& out = u->acts[o.dst];
-      const int segs = u->bf16 ? conv_gn_wide_segs(out.H, out.W, c.nb * out.H * out.W, o.Cout) : 0;
-      kind = segs == 1 ? kCensusConvGNW : segs == 4 ? kCensusConvGNW4 : kCensusConvGN;
-    }
+    if (o.kind == OP_CONV && o.coef != SIZE_MAX)
+      kind = cl.p.wide_segs == 1 ? kCensusConvGNW : cl.p.wide_segs == 4 ? kCensusConvGNW4 : kCensusConvGN;
     double fl = op_flops(u, o, c.nb);
-    if (c.census && o.kind == OP_CONV && o.sc_op >= 0) {  // + the folded shortcut's K slices (1x1, its Cin)
-      ConvArgs na{};
-      if (conv_args(u, o, c, na) == ITSD_OK && na.sc_C1 + na.sc_C2 > 0) fl += 2.0 * na.M * (double)o.Cout * (na.sc_C1 + na.sc_C2);
-    }
-    CHK(mark(kind, fl, [&]() { return launch_op(u, o, c, s); }));
+    // + the folded shortcut's K slices (1x1, its Cin)
+    if (cl.p.sc_split) fl += 2.0 * cl.a.M * (double)o.Cout * (cl.a.sc_C1 + cl.a.sc_C2);
+    CHK(mark(kind, fl, [&]() { return launch_op(u, o, c, &cl, s); }));
   }
   // tail GN + conv (+ sampler update); bf16 MFMA tail: GN coefficients, then one fused launch
   cur_op = 0;
@@ -1173,7 +1187,7 @@ int run_program(itsd_unet* u, const RunCtx& c, hipStream_t s) {
     g.kind = OP_GN;
     g.dst = u->tail_g;
   }
-  CHK(mark((int)g.kind, 0.0, [&]() { return launch_op(u, g, c, s); }));
+  CHK(mark((int)g.kind, 0.0, [&]() { return launch_op(u, g, c, nullptr, s); }));
   CHK(mark(-2, 2.0 * c.tail.n * (c.tail.cfg ? 2 : 1) * u->H * u->H * 27.0 * u->acts[u->tail_in].C, [&]() -> int {
     TailArgs t = c.tail;
     t.w = u->wp(u->tail_w);
@@ -1267,6 +1281,73 @@ int kernel_id(const char* name) {
 }
 }  // namespace itsd
 
+namespace {
+// itsd_set_option's keys (include/itsd.h lists the same set). A value outside [lo, hi] is refused, except:
+enum : unsigned {
+  kDiag = 1,   // a measured-and-dropped variant's switch (round 6): diagnostic builds only
+               // (tools/build_diag.sh); the shipped library refuses the key
+  kShip1 = 2,  // the shipped library takes [lo, 1] only (above: a diagnostic variant)
+  kBool = 4,   // any value, stored as 0 / 1
+  kSet = 8,    // the values listed in `set` (ended by -1)
+  kMask = 16,  // any value, stored & hi
+};
+struct Option {
+  const char* key;
+  int* var;
+  int lo, hi;
+  unsigned flags;
+  const char* what;
+  int set[6] = {-1, -1, -1, -1, -1, -1};
+};
+// conv_dbg (measurements only: results are wrong when set): 1 no in-loop loads (zero-page sources), 2 no MFMA, 8 no GN
+// transform, 16 no epilogue, 32 no epilogue output stores, 64 fused-conv halo loads from the zero page, 128 no GN
+// statistics pass, 256 no residual loads, 512 (wide fused conv) s_setprio 1 for waves 4-7 (results unchanged),
+// 1024 / 2048 (wide fused conv) every lane reads the same B / A fragment row (LDS broadcast). (Never skip an issued
+// load's wait: an in-flight load landing in a reused register faults.) 4096 | (mask << 13): compile-time ablations of
+// conv3x3_gn_p4_kernel<32> (conv.hip); (1 << 20) / (1 << 21): s_setprio 1 / 2 for the fused GroupNorm conv's halo waves
+constexpr int kConvDbgMask = 1 | 2 | 8 | 16 | 32 | 64 | 128 | 256 | 512 | 1024 | 2048 | 4096 | (127 << 13) | (3 << 20);
+const Option kOptions[] = {
+    {"conv_variant", &g_conv_variant, 1, 2, 0, "2 conv_pipe (shipped), 1 conv_igemm (register-staged, parity checks)"},
+    {"splitk", &g_splitk, 0, 64, kShip1, "split-K for under-filled grids: 0 off, 1 auto, >= 2 forced slice count"},
+    {"splitk_inl", &g_splitk_inl, 0, 1, 0, "conv_pipe split-K: 1 in-launch ticket combine, 0 splitk_epilogue_kernel"},
+    {"subpix_split", &g_subpix_split, 0, 1, 0, "under-filled sub-pixel conv_pipe launches split K in-launch"},
+    {"conv1x1", &g_conv1x1, 0, 2, kShip1, "streaming 1x1 kernel for statistics-free 1x1 convs of large pixel counts: 0 off, 1 on, 2 the 7-stage ring"},
+    {"small_conv", &g_small_conv, 0, 2, 0, "conv_small's 64x64 tiles at the small levels: 0 off, 1 auto, 2 whenever eligible"},
+    {"small_8x8", &g_small_8x8, 0, 1, 0, "conv_small (split K) for under-filled 8x8-level convs"},
+    {"small_wide", &g_small_wide, 0, 2, 0, "conv_small for under-filled statistics-free convs of larger images: 0 off, 1 under 256 tiles, 2 under 512"},
+    {"small_minks", &g_small_minks, 1, 64, kDiag, "conv_small split K: at least this many 64-channel K-chunks a slice"},
+    {"small_gn", &g_small_gn, 0, 1, 0, "conv_small writes its consumer GroupNorm's output (the GN launch skipped): 0 off, 1 on"},
+    {"conv_dbg", &g_conv_dbg, 0, kConvDbgMask, kDiag | kMask, "measurement-only conv ablations (a bit mask; results are wrong when set)"},
+    {"fuse_gn", &g_fuse_gn, 0, 1, kBool, "fused GroupNorm+SiLU+conv3x3 in ResBlocks (UNets created afterwards)"},
+    {"gn_wide", &g_gn_wide, 0, 2, 0, "the persistent 256-pixel fused conv: 0 off, 1 auto, 2 whenever eligible"},
+    {"gn_fold", &g_gn_fold, 0, 1, kBool, "GroupNorm finalize inside conv3x3_gn_p4 / p5_kernel: 0 off, 1 on"},
+    {"p4_w", &g_p4_w, 0, 7, 0, "levels conv3x3_gn_p4_kernel takes (bit 0 W = 8, 1 W = 16, 2 W = 32); the others run p5 / 128-pixel tiles"},
+    {"p4_xcd", &g_p4_xcd, 0, 2, kDiag, "conv3x3_gn_p4_kernel deals each XCD a contiguous range of tiles: 0 off, 1 on, 2 the 8x8 level only"},
+    {"p4_c96", &g_p4_c96, 0, 2, 0, "8x8 conv3x3_gn_p4_kernel on 96-cout tiles: 0 off, 1 auto, 2 always (Cout % 96 == 0)"},
+    {"p4_sub", &g_p4_sub, 0, 1, 0, "nearest-x2 upsample convs on conv3x3_gn_p4_kernel's sub-pixel form: 0 off, 1 on"},
+    {"p4_plain", &g_p4_plain, 0, 2, 0, "plain 3x3 stride-1 convs on conv3x3_gn_p4_kernel (halo copies the input): 0 off, 1 from 128 tiles, 2 any tile count"},
+    {"p5", &g_p5, 0, 2, 0, "conv3x3_gn_p5_kernel at 8x8: 0 off, 1 auto, 2 always (4x4: always)"},
+    {"p5_split", &g_p5_split, 0, 16, 0, "p5's K slices: 0 auto (cost model), 1..16 forced"},
+    {"p5_sc", &g_p5_sc, 0, 2, 0, "ResBlock 1x1 shortcuts as K slices of their block2 p5 conv: 0 off, 1 auto, 2 always"},
+    {"p5_pub", &g_p5_pub, 0, 1, 0, "p5's two-slice last-arriver combine: 1 only the first arriver stores its partial, 0 both (round 5; bit-identity checks)"},
+    {"p5_xl", &g_p5_xl, 0, 3, 0, "p5's split-K partials through one XCD's L2: 0 off, 1 the shared combine at 8x8 / 16x16, 2 every eligible form (A/B), 3 (shipped) 1 + the two-slice form at 8x8 / 16x16 where K <= 3456"},
+    {"p5_dist", &g_p5_dist, 0, 2, 0, "p5's split-K combine shared by every slice (co-resident grids): 0 off (last arriver), 1 on, 2 the plans of 1 combined by the last arriver (bit-identity checks)"},
+    {"p5_c64", &g_p5_c64, 0, 2, kDiag, "64-cout conv3x3_gn_p5_kernel items at 8x8 / 4x4: 0 off, 1 auto, 2 always"},
+    {"convt_prune", &g_convt_prune, 0, 1, 0, "ConvTranspose2d sub-pixel phases skip their all-zero taps (p4 / conv_pipe)"},
+    {"tap_prune", &g_tap_prune, 0, 1, kBool, "drop all-padding conv taps at build time (UNets created afterwards)"},
+    {"down_merge", &g_down_merge, 0, 1, kBool, "CFG DownSample c1 + c2 as one 5x5 conv (UNets created afterwards)"},
+    {"io_mfma", &g_io_mfma, 0, 1, kBool, "bf16 head / tail on MFMA (UNets created afterwards)"},
+    {"attn_fuse", &g_attn_fuse, 0, 1, 0, "fused AttnBlock kernel (S = 64): 0 off, 1 on (UNets created afterwards; the 16-token form was removed)"},
+    {"attn_s1", &g_attn_s1, 0, 1, 0, "one-token AttnBlock folded to GroupNorm + one 1x1 conv (UNets created afterwards)"},
+    {"attn_split", &g_attn_split, 0, 6, kSet, "attn_block_split_kernel (an image over G blocks): 0 off, 1 auto, 2 / 4 / 6 forced", {0, 1, 2, 4, 6, -1}},
+    {"attn_wide", &g_attn_wide, 0, 2, 0, "channel-split attention (attn_cs_kernel): 0 off, 1 auto (C >= 384 at S >= 256; C = 1024), 2 wherever it applies"},
+    {"attn_wide_nq", &g_attn_wide_nq, 0, 2, 0, "channel-split attention: query groups a block (0 auto, 1, 2)"},
+    {"attn_cs", &g_attn_cs, 0, 8, kDiag, "attn_mfma_kernel output-channel slices: 0 auto, 1..8 forced"},
+    {"attn_aq", &g_attn_aq, 0, 64, kDiag | kSet, "attn_mfma_kernel queries per block: 0 auto, 32, 64", {0, 32, 64, -1}},
+    {"spin_bound", &g_spin_bound, 0, 0x7fffffff, 0, "diagnostic: polls before an in-kernel hand-off wait fails (shipped 1 << 22)"},
+};
+}  // namespace
+
 extern "C" {
 
 int itsd_version(void) { return 1; }
@@ -1278,221 +1359,39 @@ const char* itsd_kernel_name(int id) {
 
 int itsd_set_option(const char* key, int value) {
   if (!key) return fail(ITSD_ERR_INVALID, "null key");
-#ifndef ITSD_DIAG
-  // (round 6) measurement switches -- the conv_dbg ablations, forced attention tilings, the XCD tile
-  // order at every level, conv_small's slice floor, forced split-K slice counts and the 7-stage 1x1 ring -- select
-  // measured-and-dropped variants: diagnostic builds only (tools/build_diag.sh). The shipped library takes the
-  // shipped choices below (auto / off / forced forms of the paths it ships, each A/B'd by a parity test).
-  for (const char* dk : {"conv_dbg", "attn_cs", "attn_aq", "p4_xcd", "small_minks", "p5_c64"})
-    if (!std::strcmp(key, dk)) return fail(ITSD_ERR_INVALID, std::string(key) + ": diagnostic builds only (tools/build_diag.sh)");
-  if (!std::strcmp(key, "splitk") && value > 1) return fail(ITSD_ERR_INVALID, "splitk in [0,1] (forced slice counts: diagnostic builds)");
-  if (!std::strcmp(key, "conv1x1") && value > 1) return fail(ITSD_ERR_INVALID, "conv1x1 in [0,1] (the 7-stage ring: diagnostic builds)");
+#ifdef ITSD_DIAG
+  const bool shipped = false;
+#else
+  const bool shipped = true;
 #endif
+  const Option* o = nullptr;
+  for (const Option& r : kOptions)
+    if (!std::strcmp(key, r.key)) o = &r;
+  if (o && shipped && (o->flags & kDiag))
+    return fail(ITSD_ERR_INVALID, std::string(key) + ": diagnostic builds only (tools/build_diag.sh)");
+  if (o && shipped && (o->flags & kShip1) && value > 1)
+    return fail(ITSD_ERR_INVALID, std::string(key) + " in [" + std::to_string(o->lo) + ",1] (above: diagnostic builds only, tools/build_diag.sh)");
   ++itsd::g_option_gen;  // cached step graphs baked in the previous kernel choices
-  if (!std::strcmp(key, "conv_variant")) {  // 2: conv_pipe (shipped); 1: conv_igemm (register-staged, parity checks)
-    if (value < 1 || value > 2) return fail(ITSD_ERR_INVALID, "conv_variant in [1,2]");
-    itsd::g_conv_variant = value;
-    return ITSD_OK;
+  if (!o) return fail(ITSD_ERR_INVALID, std::string("unknown option ") + key);
+  // validated before it is stored: a refused call leaves the previous setting in place
+  int v = value;
+  if (o->flags & kBool) {
+    v = value ? 1 : 0;
+  } else if (o->flags & kMask) {
+    v = value & o->hi;
+  } else if (o->flags & kSet) {
+    bool ok = false;
+    std::string vals;
+    for (const int* q = o->set; *q >= 0; ++q) {
+      ok |= *q == value;
+      vals += (vals.empty() ? "" : ",") + std::to_string(*q);
+    }
+    if (!ok) return fail(ITSD_ERR_INVALID, std::string(key) + " in {" + vals + "}: " + o->what);
+  } else if (value < o->lo || value > o->hi) {
+    return fail(ITSD_ERR_INVALID, std::string(key) + " in [" + std::to_string(o->lo) + "," + std::to_string(o->hi) + "]: " + o->what);
   }
-  if (!std::strcmp(key, "splitk")) {
-    if (value < 0 || value > 64) return fail(ITSD_ERR_INVALID, "splitk in [0,64]");
-    itsd::g_splitk = value;
-    return ITSD_OK;
-  }
-  if (!std::strcmp(key, "io_mfma")) {  // takes effect for UNets created afterwards
-    itsd::g_io_mfma = value ? 1 : 0;
-    return ITSD_OK;
-  }
-  if (!std::strcmp(key, "conv1x1")) {  // streaming 1x1 conv kernel for statistics-free 1x1 convs of large pixel counts
-    if (value < 0 || value > 2) return fail(ITSD_ERR_INVALID, "conv1x1 in [0,2]");
-    itsd::g_conv1x1 = value;
-    return ITSD_OK;
-  }
-  if (!std::strcmp(key, "small_8x8")) {  // conv_small (split K) for under-filled 8x8-level convs
-    if (value < 0 || value > 1) return fail(ITSD_ERR_INVALID, "small_8x8 in [0,1]");
-    itsd::g_small_8x8 = value;
-    return ITSD_OK;
-  }
-  if (!std::strcmp(key, "small_wide")) {  // conv_small for under-filled statistics-free convs of larger images
-    if (value < 0 || value > 2) return fail(ITSD_ERR_INVALID, "small_wide in [0,2]");
-    itsd::g_small_wide = value;
-    return ITSD_OK;
-  }
-  if (!std::strcmp(key, "small_conv")) {
-    if (value < 0 || value > 2) return fail(ITSD_ERR_INVALID, "small_conv in [0,2]");
-    itsd::g_small_conv = value;
-    return ITSD_OK;
-  }
-  if (!std::strcmp(key, "conv_dbg")) {  // measurements only (results are wrong when set): 1 no
-    // in-loop loads (zero-page sources), 2 no MFMA, 8 no GN transform, 16 no epilogue,
-    // 32 no epilogue output stores, 64 fused-conv halo loads from the zero page, 128 no
-    // GN statistics pass, 256 no residual loads, 512 (wide fused
-    // conv) s_setprio 1 for waves 4-7 (results unchanged), 1024 / 2048 (wide
-    // fused conv) every lane reads the same B / A fragment row (LDS broadcast). (Never skip an issued load's wait: an
-    // in-flight load landing in a reused register faults.)
-    // 4096 | (mask << 13): compile-time ablations of conv3x3_gn_p4_kernel<32> (conv.hip, diagnostic builds)
-    // (1 << 20) / (1 << 21): s_setprio 1 / 2 for the halo waves of the fused GroupNorm conv
-    const int v = value & (1 | 2 | 8 | 16 | 32 | 64 | 128 | 256 | 512 | 1024 | 2048 | 4096 | (127 << 13) | (3 << 20));
-#ifndef ITSD_DIAG
-    // validated before it is stored: a refused call leaves the previous setting in place
-    if (v & 4096) return fail(ITSD_ERR_INVALID, "conv_dbg 4096 (compile-time ablations): diagnostic builds only (tools/build_diag.sh)");
-#endif
-    itsd::g_conv_dbg = v;
-    return ITSD_OK;
-  }
-  if (!std::strcmp(key, "gn_wide")) {  // the persistent 256-pixel fused conv: 0 off, 1 auto, 2 whenever eligible
-    if (value < 0 || value > 2) return fail(ITSD_ERR_INVALID, "gn_wide in [0,2]");
-    itsd::g_gn_wide = value;
-    return ITSD_OK;
-  }
-  if (!std::strcmp(key, "attn_cs")) {  // attn_mfma_kernel output-channel slices: 0 auto, 1..8 forced
-    if (value < 0 || value > 8) return fail(ITSD_ERR_INVALID, "attn_cs in [0,8]");
-    itsd::g_attn_cs = value;
-    return ITSD_OK;
-  }
-  if (!std::strcmp(key, "attn_aq")) {  // attn_mfma_kernel queries per block: 0 auto, 32, 64
-    if (value != 0 && value != 32 && value != 64) return fail(ITSD_ERR_INVALID, "attn_aq in {0,32,64}");
-    itsd::g_attn_aq = value;
-    return ITSD_OK;
-  }
-  if (!std::strcmp(key, "p4_w")) {  // levels conv3x3_gn_p4_kernel takes (bit 0 W = 8, 1 W = 16, 2 W = 32); others p5 / 128-px
-    if (value < 0 || value > 7) return fail(ITSD_ERR_INVALID, "p4_w in [0,7]");
-    itsd::g_p4_w = value;
-    return ITSD_OK;
-  }
-  if (!std::strcmp(key, "splitk_inl")) {  // conv_pipe split-K: 1 in-launch ticket combine, 0 splitk_epilogue_kernel
-    if (value < 0 || value > 1) return fail(ITSD_ERR_INVALID, "splitk_inl in [0,1]");
-    itsd::g_splitk_inl = value;
-    return ITSD_OK;
-  }
-  if (!std::strcmp(key, "spin_bound")) {  // diagnostic: polls before an in-kernel hand-off wait fails (shipped 1 << 22)
-    if (value < 0) return fail(ITSD_ERR_INVALID, "spin_bound >= 0");
-    itsd::g_spin_bound = value;
-    return ITSD_OK;
-  }
-  if (!std::strcmp(key, "p4_xcd")) {  // conv3x3_gn_p4_kernel: deal each XCD a contiguous range of tiles (0 off, 1 on,
-                                       // 2 the 8x8 level only)
-    if (value < 0 || value > 2) return fail(ITSD_ERR_INVALID, "p4_xcd in [0,2]");
-    itsd::g_p4_xcd = value;
-    return ITSD_OK;
-  }
-  if (!std::strcmp(key, "p4_c96")) {  // 8x8 conv3x3_gn_p4_kernel on 96-cout tiles: 0 off, 1 auto, 2 always (Cout % 96 == 0)
-    if (value < 0 || value > 2) return fail(ITSD_ERR_INVALID, "p4_c96 in [0,2]");
-    itsd::g_p4_c96 = value;
-    return ITSD_OK;
-  }
-  if (!std::strcmp(key, "p4_sub")) {  // nearest-x2 upsample convs on conv3x3_gn_p4_kernel's sub-pixel form: 0 off, 1 on
-    if (value < 0 || value > 1) return fail(ITSD_ERR_INVALID, "p4_sub in [0,1]");
-    itsd::g_p4_sub = value;
-    return ITSD_OK;
-  }
-  if (!std::strcmp(key, "small_minks")) {  // conv_small split K: at least this many 64-channel K-chunks a slice
-    if (value < 1 || value > 64) return fail(ITSD_ERR_INVALID, "small_minks in [1,64]");
-    itsd::g_small_minks = value;
-    return ITSD_OK;
-  }
-  if (!std::strcmp(key, "convt_prune")) {  // ConvTranspose2d sub-pixel phases skip their all-zero taps (p4 / conv_pipe)
-    if (value < 0 || value > 1) return fail(ITSD_ERR_INVALID, "convt_prune in [0,1]");
-    itsd::g_convt_prune = value;
-    return ITSD_OK;
-  }
-  if (!std::strcmp(key, "subpix_split")) {  // under-filled sub-pixel conv_pipe launches split K in-launch
-    if (value < 0 || value > 1) return fail(ITSD_ERR_INVALID, "subpix_split in [0,1]");
-    itsd::g_subpix_split = value;
-    return ITSD_OK;
-  }
-  if (!std::strcmp(key, "p4_plain")) {  // plain 3x3 stride-1 convs on conv3x3_gn_p4_kernel (halo copies the input)
-    if (value < 0 || value > 2) return fail(ITSD_ERR_INVALID, "p4_plain in [0,2]");
-    itsd::g_p4_plain = value;
-    return ITSD_OK;
-  }
-  if (!std::strcmp(key, "p5")) {  // conv3x3_gn_p5_kernel at 8x8: 0 off, 1 auto, 2 always (4x4: always)
-    if (value < 0 || value > 2) return fail(ITSD_ERR_INVALID, "p5 in [0,2]");
-    itsd::g_p5 = value;
-    return ITSD_OK;
-  }
-  if (!std::strcmp(key, "p5_split")) {  // its K slices: 0 auto (cost model), 1..16 forced
-    if (value < 0 || value > 16) return fail(ITSD_ERR_INVALID, "p5_split in [0,16]");
-    itsd::g_p5_split = value;
-    return ITSD_OK;
-  }
-  if (!std::strcmp(key, "p5_sc")) {  // ResBlock 1x1 shortcuts as K slices of their block2 p5 conv: 0 off, 1 auto, 2 always
-    if (value < 0 || value > 2) return fail(ITSD_ERR_INVALID, "p5_sc in [0,2]");
-    itsd::g_p5_sc = value;
-    return ITSD_OK;
-  }
-  if (!std::strcmp(key, "small_gn")) {  // conv_small writes its consumer GroupNorm's output (the GN launch skipped): 0 off, 1 on
-    if (value < 0 || value > 1) return fail(ITSD_ERR_INVALID, "small_gn in [0,1]");
-    itsd::g_small_gn = value;
-    return ITSD_OK;
-  }
-  if (!std::strcmp(key, "p5_pub")) {  // p5's two-slice last-arriver combine: 1 only the first arriver stores its partial,
-                                      // 0 both slices store theirs (round 5; bit-identity checks)
-    if (value < 0 || value > 1) return fail(ITSD_ERR_INVALID, "p5_pub in [0,1]");
-    itsd::g_p5_pub = value;
-    return ITSD_OK;
-  }
-  if (!std::strcmp(key, "p5_xl")) {  // p5's split-K partials through one XCD's L2 (slices of a tile on one XCD): 0 off,
-                                     // 1 the shared combine at 8x8 / 16x16, 2 every eligible form (A/B), 3 (shipped)
-                                     // 1 + the two-slice form at 8x8 / 16x16 where K <= 3456
-    if (value < 0 || value > 3) return fail(ITSD_ERR_INVALID, "p5_xl in [0,3]");
-    itsd::g_p5_xl = value;
-    return ITSD_OK;
-  }
-  if (!std::strcmp(key, "p5_dist")) {  // p5's split-K combine shared by every slice (co-resident grids): 0 off (last arriver),
-                                       // 1 on, 2 the same plans as 1 combined by the last arriver (bit-identity checks)
-    if (value < 0 || value > 2) return fail(ITSD_ERR_INVALID, "p5_dist in [0,2]");
-    itsd::g_p5_dist = value;
-    return ITSD_OK;
-  }
-  if (!std::strcmp(key, "p5_c64")) {  // (diagnostic) 64-cout conv3x3_gn_p5_kernel items at 8x8 / 4x4: 0 off, 1 auto, 2 always
-    if (value < 0 || value > 2) return fail(ITSD_ERR_INVALID, "p5_c64 in [0,2]");
-    itsd::g_p5_c64 = value;
-    return ITSD_OK;
-  }
-  if (!std::strcmp(key, "gn_fold")) {  // GroupNorm finalize inside conv3x3_gn_p4 / p5_kernel: 0 off, 1 on
-    itsd::g_gn_fold = value ? 1 : 0;
-    return ITSD_OK;
-  }
-  if (!std::strcmp(key, "attn_split")) {  // attn_block_split_kernel (an image over G blocks): 0 off, 1 auto, 2 / 4 / 6 forced
-    if (value != 0 && value != 1 && value != 2 && value != 4 && value != 6)
-      return fail(ITSD_ERR_INVALID, "attn_split in {0, 1, 2, 4, 6}");
-    itsd::g_attn_split = value;
-    return ITSD_OK;
-  }
-  if (!std::strcmp(key, "tap_prune")) {  // drop all-padding conv taps at build time (UNets created afterwards)
-    itsd::g_tap_prune = value ? 1 : 0;
-    return ITSD_OK;
-  }
-  if (!std::strcmp(key, "down_merge")) {  // CFG DownSample c1 + c2 as one 5x5 conv (UNets created afterwards)
-    itsd::g_down_merge = value ? 1 : 0;
-    return ITSD_OK;
-  }
-  if (!std::strcmp(key, "attn_wide_nq")) {  // channel-split attention: query groups a block (0 auto, 1, 2)
-    if (value < 0 || value > 2) return fail(ITSD_ERR_INVALID, "attn_wide_nq in [0,2]");
-    itsd::g_attn_wide_nq = value;
-    return ITSD_OK;
-  }
-  if (!std::strcmp(key, "attn_wide")) {  // channel-split attention (attn_cs_kernel): 0 off, 1 auto (C >= 384 at S >= 256; C = 1024), 2 wherever it applies
-    if (value < 0 || value > 2) return fail(ITSD_ERR_INVALID, "attn_wide in [0,2]");
-    itsd::g_attn_wide = value;
-    return ITSD_OK;
-  }
-  if (!std::strcmp(key, "attn_s1")) {  // one-token AttnBlock folded to GroupNorm + one 1x1 conv (UNets created afterwards)
-    if (value < 0 || value > 1) return fail(ITSD_ERR_INVALID, "attn_s1 in [0,1]");
-    itsd::g_attn_s1 = value;
-    return ITSD_OK;
-  }
-  if (!std::strcmp(key, "attn_fuse")) {  // fused AttnBlock kernel (S = 64): 0 off, 1 on (UNets created afterwards)
-    if (value < 0 || value > 1) return fail(ITSD_ERR_INVALID, "attn_fuse in [0,1] (the 16-token form was removed)");
-    itsd::g_attn_fuse = value;
-    return ITSD_OK;
-  }
-  if (!std::strcmp(key, "fuse_gn")) {  // takes effect for UNets created afterwards
-    itsd::g_fuse_gn = value ? 1 : 0;
-    return ITSD_OK;
-  }
-  return fail(ITSD_ERR_INVALID, std::string("unknown option ") + key);
+  *o->var = v;
+  return ITSD_OK;
 }
 
 const char* itsd_last_error(void) { return g_err.c_str(); }
@@ -1609,7 +1508,7 @@ int itsd_unet_forward(itsd_unet* u, const float* x, const int32_t* t, const int3
   c.labels = labels; c.label_mod = n; c.uncond_from = -1;
   c.tail.n = n; c.tail.cfg = 0; c.tail.step_mode = 0; c.tail.eps_out = eps;
   HIPCHK(hipMemsetAsync(u->d_nan + 1, 0, 4, s));  // this forward's hand-off status (itsd_unet_query "status")
-  CHK(run_program(u, c, s));
+  CHK(run_program(u, c, resolve_program(u, c), s));
   u->last_forward_n = n;
   HIPCHK(hipEventRecord(u->ev_out, s));
   HIPCHK(hipStreamWaitEvent(cs, u->ev_out, 0));
@@ -1700,7 +1599,7 @@ int itsd_sampler_run(itsd_unet* u, float* x, const int32_t* labels, int n, int t
       if (g.key == key) exec = g.exec;
     if (!exec) {
       HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-      int r = run_program(u, c, s);
+      int r = run_program(u, c, resolve_program(u, c), s);
       if (r == ITSD_OK && launch_add_int(u->d_t, -1, s) != hipSuccess) r = fail(ITSD_ERR_HIP, "add_int");
       hipGraph_t graph = nullptr;
       hipError_t e = hipStreamEndCapture(s, &graph);
@@ -1715,8 +1614,9 @@ int itsd_sampler_run(itsd_unet* u, float* x, const int32_t* labels, int n, int t
     }
     for (int i = 0; i < steps; ++i) HIPCHK(hipGraphLaunch(exec, s));
   } else {
+    const std::vector<ConvLaunch> convs = resolve_program(u, c);  // (the steps differ in device state only)
     for (int i = 0; i < steps; ++i) {
-      CHK(run_program(u, c, s));
+      CHK(run_program(u, c, convs, s));
       HIPCHK(launch_add_int(u->d_t, -1, s));
     }
   }
@@ -1801,7 +1701,7 @@ int itsd_profile_forward(itsd_unet* u, const float* x, const int32_t* t, int n, 
   c.label_mod = n; c.uncond_from = -1;
   c.tail.n = n; c.tail.step_mode = 0; c.tail.eps_out = eps;
   c.census = true; c.evs = &evs; c.ev_kind = &kinds; c.ev_flops = &fl;
-  int r = run_program(u, c, s);
+  int r = run_program(u, c, resolve_program(u, c), s);
   hipError_t e = hipStreamSynchronize(s);
   double cm = 0, cf = 0, tm = 0;
   int cl = 0;
@@ -1850,14 +1750,16 @@ int itsd_profile_op(itsd_unet* u, const float* x, const int32_t* t, int n, int o
   c.temb = u->proj_buf; c.temb_img_stride = u->sumC;
   c.labels = lab0; c.label_mod = n; c.uncond_from = -1;
   c.tail.n = n; c.tail.step_mode = 0; c.tail.eps_out = eps;
-  if (r == ITSD_OK) r = run_program(u, c, s);  // every op's inputs in place
+  const std::vector<ConvLaunch> convs = resolve_program(u, c);
+  if (r == ITSD_OK) r = run_program(u, c, convs, s);  // every op's inputs in place
   hipEvent_t e0 = nullptr, e1 = nullptr;
   hipError_t e = hipEventCreate(&e0);
   if (e == hipSuccess) e = hipEventCreate(&e1);
   const Op& o = u->ops[op_index - 1];
-  if (r == ITSD_OK && e == hipSuccess) r = launch_op(u, o, c, s);  // warm
+  const ConvLaunch* cl = &convs[op_index - 1];
+  if (r == ITSD_OK && e == hipSuccess) r = launch_op(u, o, c, cl, s);  // warm
   if (r == ITSD_OK && e == hipSuccess) e = hipEventRecord(e0, s);
-  for (int i = 0; i < reps && r == ITSD_OK && e == hipSuccess; ++i) r = launch_op(u, o, c, s);
+  for (int i = 0; i < reps && r == ITSD_OK && e == hipSuccess; ++i) r = launch_op(u, o, c, cl, s);
   if (r == ITSD_OK && e == hipSuccess) e = hipEventRecord(e1, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   float m = 0.f;
@@ -1897,7 +1799,8 @@ int itsd_profile_ops(itsd_unet* u, const float* x, const int32_t* t, int n, int 
   c.labels = lab0; c.label_mod = n; c.uncond_from = -1;
   c.tail.n = n; c.tail.step_mode = 0; c.tail.eps_out = eps;
   c.census = true; c.evs = &evs; c.ev_kind = &kd; c.ev_flops = &fl; c.ev_kid = &kid; c.ev_op = &eop;
-  int r = run_program(u, c, s);
+  const std::vector<ConvLaunch> convs = resolve_program(u, c);
+  int r = run_program(u, c, convs, s);
   hipError_t e = hipStreamSynchronize(s);
   // launch order: head, ops..., tail GN, tail
   int k = 0;
@@ -1927,10 +1830,10 @@ int itsd_profile_ops(itsd_unet* u, const float* x, const int32_t* t, int n, int 
         // flags for the algorithmic-bytes count (bench.py conv_alg_bytes): bit 0 a residual operand, bit 1 the
         // output's GroupNorm statistics written, bit 2 the input GroupNorm(+SiLU) fused (its statistics read)
         sh[7] = (o.resid >= 0 ? 1 : 0) | (out.stats != SIZE_MAX ? 2 : 0) | (o.coef != SIZE_MAX ? 4 : 0);
-        if (o.kind == OP_CONV && o.sc_op >= 0) {  // a block2 conv with its 1x1 shortcut folded in as K slices: no
-          ConvArgs na{};                          // residual operand; the shortcut's input channels in bits 8..
-          if (conv_args(u, o, c, na) == ITSD_OK && na.sc_C1 + na.sc_C2 > 0) sh[7] = (sh[7] & ~1) | ((na.sc_C1 + na.sc_C2) << 8);
-        }
+        // a block2 conv with its 1x1 shortcut folded in as K slices: no residual operand; the shortcut's input
+        // channels in bits 8..
+        const ConvLaunch& cl = convs[eop[i] - 1];
+        if (cl.p.sc_split) sh[7] = (sh[7] & ~1) | ((cl.a.sc_C1 + cl.a.sc_C2) << 8);
       }
     }
     ++k;

@@ -59,6 +59,11 @@ typedef uint16_t bf16_t;  // storage type for bf16 activations / weights
 // use this one constant.
 constexpr long long kTicketCap = 16384;
 
+// nn.GroupNorm(32, C, eps=1e-5) (Model.py:132,171,180,253): the host's GNArgs::eps and group arithmetic, and
+// conv_small's fused GroupNorm epilogue
+constexpr int kGnGroups = 32;
+constexpr float kGnEps = 1e-5f;
+
 typedef __attribute__((ext_vector_type(8))) short bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
@@ -196,6 +201,43 @@ struct ConvArgs {
   const float* go_beta;
   int go_silu;
 };
+
+// How launch_conv runs one conv: every decision between the ConvArgs and the launch, made once by plan_conv (conv.hip,
+// host only) and shared with the host program (api.hip: the GroupNorm / shortcut folds, the census).
+enum class ConvKernel {
+  P5,           // conv3x3_gn_p5_kernel<W>, split-K combined by each tile's last-arriving slice
+  P5_SHARED,    // conv3x3_gn_p5_kernel<W, 128, true>: the combine shared by every slice (kdist)
+  P4_GN,        // conv3x3_gn_p4_kernel<W>: fused GroupNorm, 256 pixels x 128 couts
+  P4_C96,       // conv3x3_gn_p4_kernel<8, 512>: ... on 96-cout tiles
+  P4_PLAIN,     // conv3x3_gn_p4_kernel<W, 2>: no GroupNorm
+  P4_SUB,       // conv3x3_gn_p4_kernel<W, 128>: the 2x2-tap phases of a nearest-x2 upsample conv
+  P4_CONVT,     // conv3x3_gn_p4_kernel<W, 384>: the 3x3-tap phases of ConvTranspose2d(5, 2, 2, 1)
+  GN128,        // conv3x3_gn_kernel<gn_segs>: fused GroupNorm, 128 x 128 tiles
+  STREAM1X1,    // conv1x1_stream_kernel<Cin, 4 | 7>
+  SMALL,        // conv_small<false>: 64 x 64 tiles, grid.z K slices combined in-launch
+  PIPE_LIN,     // conv_pipe<T, 2, true>: plain stride / pad addressing
+  PIPE,         // conv_pipe<T, 2, false>: nearest-x2 upsample / zero insertion folded into the addressing
+  PIPE_SUBPIX,  // conv_pipe<T, 2, true> over 4 sub-pixel phases (grid.z = 4 x K slices)
+  IGEMM,        // conv_igemm<T>: register-staged fallback
+};
+struct ConvPlan {
+  bool valid = true;  // false: a shape no kernel takes (launch_conv returns hipErrorInvalidValue)
+  ConvKernel kernel = ConvKernel::IGEMM;
+  dim3 grid;
+  int block = 256;
+  // p5 (copied into ConvArgs::ksplit / sc_split / kdist / kpub / kxl by launch_conv); cb: its cout tile (128; 64 in
+  // diagnostic builds). sc_split > 0: the args' sc_* shortcut is folded in (0: the caller drops it and launches the
+  // shortcut conv itself)
+  int ksplit = 1, sc_split = 0, cb = 128, kdist = 0, kpub = 0, kxl = 0;
+  // K slices of conv_small / conv_pipe (in grid.z). conv_pipe combines them in-launch on the args' tickets (inl) or,
+  // without tickets, by a splitk_epilogue_kernel launch over grid.x x grid.y (epilogue)
+  int S = 1;
+  bool inl = true, epilogue = false;
+  int gn_segs = 0;    // GN128: images a 128-pixel tile spans (1 | 2)
+  int wide_segs = 0;  // fused GroupNorm convs: 1 rows of one image / 4 four 8x8 images a 256-pixel tile, 0 neither
+                      // (the census kind)
+};
+ConvPlan plan_conv(const ConvArgs& a, bool bf16);
 
 // Channel-statistics slab of an NHWC tensor (written by its producer): slots of
 // Gt = min(HW, 128) consecutive pixels; stats[slot][0][c] = sum, [slot][1][c] = sum of squares.

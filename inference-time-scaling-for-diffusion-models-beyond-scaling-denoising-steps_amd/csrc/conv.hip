@@ -15,11 +15,12 @@
 //
 // Two main loops:
 //  * conv_pipe (every shape whose input channels split into whole 128-B K-chunks,
-//    i.e. all Arch A/C layers): a 4-stage LDS ring filled by global_load_lds
-//    (HBM/L2 -> LDS DMA, 1 KiB per wave-instruction, inverse-swizzled per-lane
-//    source address; padded / out-of-range rows read a zero page), counted
-//    s_waitcnt vmcnt + raw s_barrier so three stages stay in flight while one is
-//    consumed -- the loop is otherwise load-latency bound.
+//    i.e. all Arch A/C layers): an NS-stage LDS ring (shipped: NS = 2, two blocks
+//    a CU; the 3- / 4-stage rings measured slower and were removed in round 5)
+//    filled by global_load_lds (HBM/L2 -> LDS DMA, 1 KiB per wave-instruction,
+//    inverse-swizzled per-lane source address; padded / out-of-range rows read a
+//    zero page), counted s_waitcnt vmcnt + raw s_barrier so NS - 1 stages stay in
+//    flight while one is consumed -- the loop is otherwise load-latency bound.
 //  * conv_igemm (generic fallback): register-staged double buffer.
 // Epilogue (shared, LDS-staged): + bias + temb_proj row (+ CFG cond_proj row) +
 // residual, coalesced 16-B stores, and the consumer GroupNorm's channel statistics.
@@ -61,7 +62,7 @@ int g_p4_xcd = 2;        // conv3x3_gn_p4_kernel: each XCD a contiguous range of
                          // level (measured -2 % at N = 256), 2 the 8x8 level only (a pixel tile's cout tiles on one
                          // XCD: its input read once per L2; 8x8 HBM traffic 98.5 -> 65.1 MB a launch at equal step
                          // time, profiles/r05/p4_xcd8_traffic_r05s.txt)
-int g_p4_c96 = 1;        // 8x8 p4 on 96-cout tiles where they fill the CUs better: 0 off, 1 auto, 2 always (conv_p4_c96)
+int g_p4_c96 = 1;        // 8x8 p4 on 96-cout tiles where they fill the CUs better: 0 off, 1 auto, 2 always (p4_c96)
 int g_p4_sub = 1;        // nearest-x2 upsample convs on conv3x3_gn_p4_kernel's sub-pixel form (AB = 128)
 int g_p5 = 1;            // conv3x3_gn_p5_kernel at 8x8: 0 off, 1 auto (where p4 has < 192 tiles), 2 always (4x4: always)
 int g_p5_split = 0;      // its K slices: 0 auto, >= 1 forced
@@ -216,7 +217,7 @@ __device__ __forceinline__ void gn_out_from_E(const ConvArgs& a, const float* E,
   constexpr int ER = BM + 4, EPC = 16 / (int)sizeof(T), CPR = BM / EPC;
   static_assert(EPC == 8, "bf16 chunks");
   const int tid = threadIdx.x, NT = blockDim.x;
-  const int HWo = a.Hout * a.Wout, gs = a.Cout / 32;
+  const int HWo = a.Hout * a.Wout, gs = a.Cout / kGnGroups;
   const int nimg = BN / HWo, ngrp = BM / gs, npairs = nimg * ngrp;
   const int img0 = tileP / HWo;
   // this thread's output chunk columns (the same for every row it stores: NT % CPR == 0), whose gamma / beta the
@@ -251,7 +252,7 @@ __device__ __forceinline__ void gn_out_from_E(const ConvArgs& a, const float* E,
     double var = qd / En - mean * mean;
     var = var > 0.0 ? var : 0.0;
     gst[2 * pr] = (float)mean;
-    gst[2 * pr + 1] = (float)(1.0 / sqrt(var + (double)1e-5f));
+    gst[2 * pr + 1] = (float)(1.0 / sqrt(var + (double)kGnEps));
   }
   // LDS writes drained, then the block barrier alone (a __syncthreads would also wait for the gamma / beta loads)
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1582,13 +1583,13 @@ constexpr int P4_RING = 6;  // A k-step slots (prefetch distance 5 k-steps = 40 
                             // of a chunk, so the slots of the next chunk's prefetched steps line up
 constexpr int P4_BD = 2;    // B fragment buffers (reads P4_BD - 1 k-steps = 8 MFMAs ahead)
 // AB: bit 1 (value 2) = plain conv3x3 (no GroupNorm+SiLU: the halo waves copy the input; shipped, the
-// CFG UpSample's 3x3 conv, conv_p4_plain_selected); bit 7 (value 128) = a sub-pixel phase conv (plain):
+// CFG UpSample's 3x3 conv, p4_plain_selected); bit 7 (value 128) = a sub-pixel phase conv (plain):
 // W is the INPUT grid, a tile is (phase, 256 input-grid pixels, 128 couts) with the phase's weights
 // (wfrag [4 phases][Cout/32][K/16]), outputs scattered to (2i + py, 2j + px) of the 2x grid and the
 // statistics slots of each (image, phase) -- 4 taps at halo offsets (dy + py, dx + px) for a nearest-x2
 // upsample + conv3x3 (Model.py:121-126, the phase's 2x2 folded taps), or with bit 8 (value 256) the 9
 // taps of a 3x3 window for ConvTranspose2d(5, 2, 2, 1) (ModelCondition.py:80, the phase's taps of the 5x5
-// kernel) (conv_p4_sub_selected); the other bits are diagnostic ablations (ITSD_DIAG).
+// kernel) (p4_sub_selected); the other bits are diagnostic ablations (ITSD_DIAG).
 template <int W, int AB = 0>
 __global__ __launch_bounds__(512, 1) void conv3x3_gn_p4_kernel(ConvArgs a) {
   typedef bf16_t T;
@@ -3934,9 +3935,9 @@ bool conv_gn_eligible(int H, int W) {
   return segs <= 2 && segs * (THs + 2) * (W + 2) <= GNC_HALO_ROWS;
 }
 
-// Which fused GroupNorm conv launch_conv runs at this shape: 0 = conv3x3_gn_kernel (128 x 128),
-// 1 / 4 = conv3x3_gn_wide_kernel<1 | 4> (256 pixels = rows of one image | four 8x8 images).
-int conv_gn_wide_segs(int H, int W, int M, int Cout, bool any_tiles = false) {
+// The 256-pixel tile of conv3x3_gn_p4_kernel at this shape (ConvPlan::wide_segs): 1 = rows of one image, 4 = four
+// 8x8 images; 0 = none, or too few tiles to fill the chip (conv3x3_gn_kernel's 128 x 128 tiles).
+static int gn_wide_segs(int H, int W, int M, int Cout, bool any_tiles = false) {
   if (!g_gn_wide || W > GNW_BN || GNW_BN % W || M % GNW_BN) return 0;
   int segs = 0;
   if (GNW_BN / W <= H) {
@@ -3996,11 +3997,10 @@ static int p5_split(const ConvArgs& a, int tiles, int nch, int cb, double fc) {
   return S;
 }
 
-bool conv_p5_selected(const ConvArgs& a);
-// launch_conv's kernel choice for a fused GroupNorm conv: conv3x3_gn_p4_kernel (any form)?
+// The predicates below are plan_conv's: it asks them in its priority order, each once.
 // 96-cout tiles of conv3x3_gn_p4_kernel<8> (AB 512)? Where the 128-cout tile count leaves CUs idle and 96-cout
 // tiles need fewer tile-rounds x tile cost (ceil(NT / CUs) x BM / 128), e.g. N = 256: 192 -> 256 tiles
-bool conv_p4_c96(const ConvArgs& a) {
+static bool p4_c96(const ConvArgs& a) {
   if (!g_p4_c96 || a.Wout != 8 || a.Cout % 96 || a.M % GNW_BN || ITSD_P4_M16 < 2) return false;
   const long long npt = a.M / GNW_BN, G = g_num_cus;
   const long long t96 = npt * (a.Cout / 96), r96 = (t96 + G - 1) / G;
@@ -4008,23 +4008,24 @@ bool conv_p4_c96(const ConvArgs& a) {
   const long long t128 = npt * (a.Cout / CONV_BM), r128 = (t128 + G - 1) / G;
   return g_p4_c96 == 2 || 3 * r96 * 100 < 4 * r128 * 97;  // 0.75 r96 < 0.97 r128
 }
-bool conv_p4_selected(const ConvArgs& a) {
-  if (!a.gn_coef || conv_p5_selected(a) || !conv_gn_wide_segs(a.Hout, a.Wout, a.M, a.Cout)) return false;
-  if (conv_p4_c96(a)) return a.wfrag && a.Hout == a.Wout && a.C1 + a.C2 >= 128 && (g_p4_w & 1);
-  return a.wfrag && a.Cout % CONV_BM == 0 && a.Hout == a.Wout && a.C1 + a.C2 >= 128 &&
+// conv3x3_gn_p4_kernel for a fused GroupNorm conv that p5 leaves and whose shape has 256-pixel tiles (gn_wide_segs)?
+static bool p4_gn_selected(const ConvArgs& a, bool c96) {
+  if (!a.wfrag || a.Hout != a.Wout || a.C1 + a.C2 < 128) return false;
+  if (c96) return (g_p4_w & 1) != 0;
+  return a.Cout % CONV_BM == 0 &&
          ((a.Wout == 32 && (g_p4_w & 4)) || (a.Wout == 16 && (g_p4_w & 2)) || (a.Wout == 8 && (g_p4_w & 1)));
 }
 
 // A plain (no GroupNorm) 3x3 stride-1 conv on conv3x3_gn_p4_kernel<W, 2>? (the CFG UpSample's conv
 // after its ConvTranspose2d: 32x32 / 16x16 / 8x8, ModelCondition.py UpSample)
-bool conv_p4_plain_selected(const ConvArgs& a) {
+static bool p4_plain_selected(const ConvArgs& a) {
   if (!g_p4_plain || a.gn_coef || !a.wfrag || a.ksize != 3 || a.stride != 1 || a.pad != 1 || a.subpix || a.upsample ||
       a.zins || a.vt_out || !a.zero || a.K != 9 * (a.C1 + a.C2) || a.C1 % 64 || a.C2 % 64)
     return false;
   // (down to 128 tiles, half the CUs: the CFG 8x8 UpSample conv at 2N = 64, 145 -> 113 us against conv_pipe,
   // profiles/r04/census_archC_2N64_p4_plain_128.txt; p4_plain = 2: any tile count)
   const long long tiles = (a.M % GNW_BN) ? 0 : (long long)(a.M / GNW_BN) * (a.Cout / CONV_BM);
-  if (!conv_gn_wide_segs(a.Hout, a.Wout, a.M, a.Cout, g_p4_plain == 2 || tiles >= 128)) return false;
+  if (!gn_wide_segs(a.Hout, a.Wout, a.M, a.Cout, g_p4_plain == 2 || tiles >= 128)) return false;
   return a.Cout % CONV_BM == 0 && a.Hout == a.Wout && a.Hin == a.Hout && a.C1 + a.C2 >= 128 &&
          (a.Wout == 32 || a.Wout == 16 || a.Wout == 8);
 }
@@ -4032,7 +4033,7 @@ bool conv_p4_plain_selected(const ConvArgs& a) {
 // A sub-pixel phase conv on conv3x3_gn_p4_kernel<W, 128 | 256 x (ConvTranspose2d)>? subpix 1: the 2x2-tap
 // phases of a nearest-x2 upsample conv; subpix 2: the 3x3-tap phases of ConvTranspose2d(5, 2, 2, 1). W = the
 // input grid (8 / 16 / 32); auto from 64 tiles of 4 phases x 256 pixels x 128 couts (192 until round 6)
-bool conv_p4_sub_selected(const ConvArgs& a) {
+static bool p4_sub_selected(const ConvArgs& a) {
   const int taps = a.subpix == 1 ? 4 : 9;
   if (!g_p4_sub || !a.subpix || !a.wfrag || a.ksize * a.ksize != taps || a.resid || a.vt_out || !a.zero ||
       a.gn_coef || a.Hout != a.Wout || !(a.Wout == 8 || a.Wout == 16 || a.Wout == 32) || a.Cout % CONV_BM ||
@@ -4042,8 +4043,8 @@ bool conv_p4_sub_selected(const ConvArgs& a) {
   return 4LL * (a.M / GNW_BN) * (a.Cout / CONV_BM) >= 64;
 }
 
-// launch_conv's kernel choice for a fused GroupNorm conv: conv3x3_gn_p5_kernel?
-bool conv_p5_selected(const ConvArgs& a) {
+// conv3x3_gn_p5_kernel for a fused GroupNorm conv?
+static bool p5_selected(const ConvArgs& a) {
   if (!a.gn_coef || !a.wfrag || a.Cout % CONV_BM || a.C1 % 64 || a.C2 % 64 || !p5_eligible(a.Hout, a.Wout)) return false;
   const int p4_tiles = (a.M % GNW_BN) ? 0 : (a.M / GNW_BN) * (a.Cout / CONV_BM);
   // (4x4: no other persistent fused kernel holds it; 64x64 on p5 unless p4_w bit 3 is set)
@@ -4059,6 +4060,7 @@ bool conv_p5_selected(const ConvArgs& a) {
 // (0: not folded) and the S to run with.
 struct P5Plan {
   int cb = 128, s = 1, s2 = 0;  // cout tile, 3x3 K slices, folded-shortcut K slices (0: not folded)
+  int tiles = 0;                // (128-pixel tiles) x (cb-cout tiles)
   double cost = 0.0;
 };
 // 64-cout p5 items at W <= 8: 0 off (shipped), 1 auto (cost model), 2 always ("p5_c64", diagnostic builds). Measured and
@@ -4087,6 +4089,7 @@ static P5Plan p5_plan(const ConvArgs& a) {
     };
     P5Plan p;
     p.cb = cb;
+    p.tiles = tiles;
     p.s = ws ? p5_split(a, tiles, nch, cb, fc) : 1;
     p.cost = cost(p.s, 0) + (sc ? ITSD_P5_SC_LAUNCH : 0.0);  // (unfolded: the shortcut's own launch besides)
     if (sc && (long long)tiles * 4 <= kTicketCap) {
@@ -4110,83 +4113,39 @@ static P5Plan p5_plan(const ConvArgs& a) {
   return best;
 }
 
-// launch_conv's shortcut fold for a p5 conv carrying sc_* candidates: folded?
-bool conv_p5_sc_fold(const ConvArgs& a) { return conv_p5_selected(a) && p5_plan(a).s2 > 0; }
-
-static hipError_t launch_p5(const ConvArgs& a0, hipStream_t s) {
-  ConvArgs a = a0;
-  const int HW = a.Hout * a.Wout, nimg = a.M / HW;
-  const int ptiles = HW > 128 ? a.M / 128 : (nimg + 128 / HW - 1) / (128 / HW);
-  const P5Plan p = p5_plan(a);
-  if (a.sc_C1 + a.sc_C2 && !p.s2) return hipErrorInvalidValue;  // (the caller folds only what p5_plan accepts)
-  const int tiles = ptiles * (a.Cout / p.cb);
-  a.ksplit = p.s;
-  a.sc_split = p.s2;
-  const int items = tiles * (p.s + p.s2);
-  a.kdist = g_p5_dist == 1 && p.cb == 128 && p5_dist(tiles, p.s + p.s2, a.Wout);
-  a.kpub = g_p5_pub;
-  const dim3 g(std::min(items, g_num_cus));
+// The p5 launch: p5_plan's slices and cout tile, then the combine's form (kdist / kpub / kxl) and the persistent grid
+static ConvPlan plan_p5(const ConvArgs& a, ConvPlan p) {
+  const P5Plan q = p5_plan(a);
+  const int ST = q.s + q.s2, items = q.tiles * ST;
+  p.cb = q.cb;
+  p.ksplit = q.s;
+  p.sc_split = q.s2;
+  p.kdist = g_p5_dist == 1 && q.cb == 128 && p5_dist(q.tiles, ST, a.Wout);  // (items <= CUs: 128-cout tiles at W <= 32)
+  p.kpub = g_p5_pub;
+  p.kernel = p.kdist ? ConvKernel::P5_SHARED : ConvKernel::P5;
+  p.grid = dim3(std::min(items, g_num_cus));
+  p.block = 512;
   {  // XCD-local exchange: the ST slices of a tile are adjacent items; every XCD's contiguous range of G / 8 blocks
      // (and so of each item round) holds whole tiles when ST divides G / 8
-    const int ST = p.s + p.s2, G = (int)g.x;
+    const int G = (int)p.grid.x;
     // 1: the shared combine at the 8x8 / 16x16 levels (N = 16 step -1.2..2.4 %, N = 32 -0.1..0.9 %); the other forms
     // mostly lose more to the slice-major order's weight re-reads than the L2 exchange saves (the 4x4 level, the
     // two-slice form at K >= 4608 and at 32x32: N = 256 +1.1 % with every form, profiles/r06/p5_xl_ops_r06as.txt);
     // 2 takes every eligible form (A/B); 3 (shipped) adds the two-slice form where K <= 3456 at 8x8 / 16x16
     // (N = 32 -1.0 % against 1, N = 16 / 64 / 256 equal: profiles/r06/stepab_p5_xl3_r06ax.txt)
     // (3: K <= 3456 -- a cout tile's whole K of weights, <= 885 KB, per XCD)
-    const bool pub = a.kpub && ST == 2, dist8 = a.kdist && a.Wout >= 8;
-    const bool form = g_p5_xl == 2 ? (a.kdist || pub)
+    const bool pub = p.kpub && ST == 2, dist8 = p.kdist && a.Wout >= 8;
+    const bool form = g_p5_xl == 2 ? (p.kdist || pub)
                       : g_p5_xl == 3 ? (dist8 || (pub && (a.Wout == 8 || a.Wout == 16) && a.K <= 3456))
                                      : dist8;
-    a.kxl = g_p5_xl && ST > 1 && form && G % 8 == 0 && (G / 8) % ST == 0;
+    p.kxl = g_p5_xl && ST > 1 && form && G % 8 == 0 && (G / 8) % ST == 0;
   }
-  if (a.kdist) {  // (items <= CUs: 128-cout tiles at W <= 32)
-    if (a.Wout == 32) ITSD_LAUNCH((conv3x3_gn_p5_kernel<32, 128, true>), g, dim3(512), 0, s, a);
-    else if (a.Wout == 16) ITSD_LAUNCH((conv3x3_gn_p5_kernel<16, 128, true>), g, dim3(512), 0, s, a);
-    else if (a.Wout == 8) ITSD_LAUNCH((conv3x3_gn_p5_kernel<8, 128, true>), g, dim3(512), 0, s, a);
-    else if (a.Wout == 4) ITSD_LAUNCH((conv3x3_gn_p5_kernel<4, 128, true>), g, dim3(512), 0, s, a);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
-  }
-  if (a.Wout == 64) ITSD_LAUNCH(conv3x3_gn_p5_kernel<64>, g, dim3(512), 0, s, a);
-  else if (a.Wout == 32) ITSD_LAUNCH(conv3x3_gn_p5_kernel<32>, g, dim3(512), 0, s, a);
-  else if (a.Wout == 16) ITSD_LAUNCH(conv3x3_gn_p5_kernel<16>, g, dim3(512), 0, s, a);
-#ifdef ITSD_DIAG
-  else if (a.Wout == 8 && p.cb == 64) ITSD_LAUNCH((conv3x3_gn_p5_kernel<8, 64>), g, dim3(512), 0, s, a);
-  else if (p.cb == 64) ITSD_LAUNCH((conv3x3_gn_p5_kernel<4, 64>), g, dim3(512), 0, s, a);
-#endif
-  else if (a.Wout == 8) ITSD_LAUNCH(conv3x3_gn_p5_kernel<8>, g, dim3(512), 0, s, a);
-  else ITSD_LAUNCH(conv3x3_gn_p5_kernel<4>, g, dim3(512), 0, s, a);
-  return hipGetLastError();
+  return p;
 }
 
-#ifdef ITSD_DIAG
-// Diagnostic builds: the compile-time ablations of conv3x3_gn_p4_kernel<32> (conv_dbg 4096 | AB << 13)
-static hipError_t launch_p4_ablation(const ConvArgs& a, dim3 gp, hipStream_t s) {
-  switch ((g_conv_dbg >> 13) & 127) {
-    case 2: ITSD_LAUNCH((conv3x3_gn_p4_kernel<32, 2>), gp, dim3(512), 0, s, a); break;
-    case 4: ITSD_LAUNCH((conv3x3_gn_p4_kernel<32, 4>), gp, dim3(512), 0, s, a); break;
-    case 8: ITSD_LAUNCH((conv3x3_gn_p4_kernel<32, 8>), gp, dim3(512), 0, s, a); break;
-    case 16: ITSD_LAUNCH((conv3x3_gn_p4_kernel<32, 16>), gp, dim3(512), 0, s, a); break;
-    case 24: ITSD_LAUNCH((conv3x3_gn_p4_kernel<32, 24>), gp, dim3(512), 0, s, a); break;
-    case 10: ITSD_LAUNCH((conv3x3_gn_p4_kernel<32, 10>), gp, dim3(512), 0, s, a); break;
-    case 32: ITSD_LAUNCH((conv3x3_gn_p4_kernel<32, 32>), gp, dim3(512), 0, s, a); break;
-    case 64: ITSD_LAUNCH((conv3x3_gn_p4_kernel<32, 64>), gp, dim3(512), 0, s, a); break;
-    case 18: ITSD_LAUNCH((conv3x3_gn_p4_kernel<32, 18>), gp, dim3(512), 0, s, a); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
-
-#endif
-
-// conv_small's K slices when launch_conv runs this (bf16, statistics-free or whole-image) conv on it, else 0 (shared
-// by launch_conv and the host's GroupNorm-output fusion, api.hip conv_args, so that both see one decision).
-int conv_small_split(const ConvArgs& a) {
-  if (a.gn_coef || conv_p4_plain_selected(a)) return 0;
-  if (conv1x1_stream_grid(a)) return 0;
-  const dim3 grid((a.M + CONV_BN - 1) / CONV_BN, (a.Cout + CONV_BM - 1) / CONV_BM);
+// conv_small's K slices where it takes this bf16 conv (one that the fused GroupNorm kernels, p4's plain form and
+// conv1x1_stream_kernel have left), else 0. grid: the conv's 128 x 128 tiles
+static int small_split(const ConvArgs& a, dim3 grid) {
   // small levels: 64 x 64 tiles, whole K per block (auto: the 4x4 level and below, where
   // 128 x 128 tiles need split-K; measured slower than conv_pipe at 8x8)
   // (auto: not for K >= 7168 or Cout >= 1536, where the 128-tile pipe with split-K measured
@@ -4222,139 +4181,220 @@ int conv_small_split(const ConvArgs& a) {
   return 0;
 }
 
-template <typename T>
-hipError_t launch_conv(const ConvArgs& a, hipStream_t s) {
-  // (the consumer GroupNorm's output is written by conv_small's epilogue only: host sets gn_out where it runs)
-  if (a.gn_out && (sizeof(T) != 2 || !conv_small_split(a))) return hipErrorInvalidValue;
-  if constexpr (sizeof(T) == 2) {
-    if (a.gn_coef) {
-      // the 4x4 level always (no other fused kernel holds it); the others where p4 under-fills the chip
-      if (conv_p5_selected(a)) return launch_p5(a, s);
-      if (const int segs = conv_gn_wide_segs(a.Hout, a.Wout, a.M, a.Cout)) {
-        if (conv_p4_selected(a)) {
-          // persistent, one MFMA wave per SIMD (512 threads, 256 registers a wave)
-          const bool c96 = conv_p4_c96(a);
-          const int tiles = (a.M / GNW_BN) * (a.Cout / (c96 ? 96 : CONV_BM));
-          const dim3 gp(std::min(tiles, g_num_cus));
-#ifdef ITSD_DIAG
-          if ((g_conv_dbg & 4096) && a.Wout == 32) return launch_p4_ablation(a, gp, s);
-#endif
-          if (a.Wout == 32) ITSD_LAUNCH(conv3x3_gn_p4_kernel<32>, gp, dim3(512), 0, s, a);
-          else if (a.Wout == 16) ITSD_LAUNCH(conv3x3_gn_p4_kernel<16>, gp, dim3(512), 0, s, a);
-          else if (c96) ITSD_LAUNCH((conv3x3_gn_p4_kernel<8, 512>), gp, dim3(512), 0, s, a);
-          else ITSD_LAUNCH(conv3x3_gn_p4_kernel<8>, gp, dim3(512), 0, s, a);
-          return hipGetLastError();
-        }
-      }
-      dim3 grid((a.M + CONV_BN - 1) / CONV_BN, (a.Cout + CONV_BM - 1) / CONV_BM);
-      const int THs = std::min(a.Hout, 128 / a.Wout), segs = 128 / (THs * a.Wout);
-      if (segs == 1) ITSD_LAUNCH(conv3x3_gn_kernel<1>, grid, dim3(256), 0, s, a);
-      else ITSD_LAUNCH(conv3x3_gn_kernel<2>, grid, dim3(256), 0, s, a);
-      return hipGetLastError();
-    }
+// Every decision between a conv's arguments and its launch, in priority order. Pure: it reads the g_* options and
+// g_num_cus and makes no HIP call, so the host program (api.hip) asks it for the folds it builds into the arguments
+// and launch_conv runs exactly what it answered. The arguments may carry a candidate shortcut (sc_*): sc_split says
+// whether it is folded; nothing else in the plan depends on an unfolded candidate.
+ConvPlan plan_conv(const ConvArgs& a, bool bf16) {
+  ConvPlan p;
+  const int Cin = a.C1 + a.C2;
+  const dim3 grid((a.M + CONV_BN - 1) / CONV_BN, (a.Cout + CONV_BM - 1) / CONV_BM);  // 128 x 128 tiles
+  const int tiles256 = (a.M / GNW_BN) * (a.Cout / CONV_BM);                           // p4's 256 x 128 tiles
+  // persistent, one MFMA wave per SIMD (512 threads, 256 registers a wave)
+  auto persistent = [&p](ConvKernel k, int tiles) {
+    p.kernel = k;
+    p.grid = dim3(std::min(tiles, g_num_cus));
+    p.block = 512;
+    return p;
+  };
+  if (bf16 && a.gn_coef) {
+    p.wide_segs = gn_wide_segs(a.Hout, a.Wout, a.M, a.Cout);
+    // the 4x4 level always (no other fused kernel holds it); the others where p4 under-fills the chip
+    if (p5_selected(a)) return plan_p5(a, p);
+    const bool c96 = p4_c96(a);
+    if (p.wide_segs && p4_gn_selected(a, c96))
+      return c96 ? persistent(ConvKernel::P4_C96, (a.M / GNW_BN) * (a.Cout / 96)) : persistent(ConvKernel::P4_GN, tiles256);
+    const int THs = std::min(a.Hout, 128 / a.Wout);
+    p.kernel = ConvKernel::GN128;
+    p.gn_segs = 128 / (THs * a.Wout);
+    p.grid = grid;
+    return p;
   }
-  constexpr int BK = 8 * (16 / (int)sizeof(T));
-  dim3 grid((a.M + CONV_BN - 1) / CONV_BN, (a.Cout + CONV_BM - 1) / CONV_BM);
-  if constexpr (sizeof(T) == 2) {
-    if (conv_p4_plain_selected(a)) {
-      const dim3 gp(std::min((a.M / GNW_BN) * (a.Cout / CONV_BM), g_num_cus));
-      if (a.Wout == 32) ITSD_LAUNCH((conv3x3_gn_p4_kernel<32, 2>), gp, dim3(512), 0, s, a);
-      else if (a.Wout == 16) ITSD_LAUNCH((conv3x3_gn_p4_kernel<16, 2>), gp, dim3(512), 0, s, a);
-      else ITSD_LAUNCH((conv3x3_gn_p4_kernel<8, 2>), gp, dim3(512), 0, s, a);
-      return hipGetLastError();
-    }
-  }
-  if constexpr (sizeof(T) == 2) {
+  if (bf16) {
+    if (p4_plain_selected(a)) return persistent(ConvKernel::P4_PLAIN, tiles256);
     // streaming 1x1 convs: >= 4 pixel tiles per persistent block (large pixel counts, N = 256)
     if (const int G = conv1x1_stream_grid(a)) {
-      {
-        const int Cin = a.C1 + a.C2;
-#define ITSD_S1(NS)                                                                          \
-  if (Cin == 128) ITSD_LAUNCH((conv1x1_stream_kernel<128, NS>), dim3(G), dim3(256), 0, s, a);      \
-  else if (Cin == 256) ITSD_LAUNCH((conv1x1_stream_kernel<256, NS>), dim3(G), dim3(256), 0, s, a); \
-  else if (Cin == 384) ITSD_LAUNCH((conv1x1_stream_kernel<384, NS>), dim3(G), dim3(256), 0, s, a); \
-  else if (Cin == 512) ITSD_LAUNCH((conv1x1_stream_kernel<512, NS>), dim3(G), dim3(256), 0, s, a); \
-  else ITSD_LAUNCH((conv1x1_stream_kernel<640, NS>), dim3(G), dim3(256), 0, s, a);
-        if (g_conv1x1 == 2) {
-          ITSD_S1(7)
-        } else {
-          ITSD_S1(4)
-        }
-#undef ITSD_S1
-        return hipGetLastError();
-      }
+      p.kernel = ConvKernel::STREAM1X1;
+      p.grid = dim3(G);
+      return p;
     }
-    if (const int S = conv_small_split(a)) {
-      const dim3 gs((a.M + SM_B - 1) / SM_B, (a.Cout + SM_B - 1) / SM_B, S);
-      ITSD_LAUNCH(conv_small<false>, gs, dim3(256), 0, s, a);
-      return hipGetLastError();
+    if (const int S = small_split(a, grid)) {
+      p.kernel = ConvKernel::SMALL;
+      p.S = S;
+      p.grid = dim3((a.M + SM_B - 1) / SM_B, (a.Cout + SM_B - 1) / SM_B, S);
+      return p;
     }
   }
-  const int Cin = a.C1 + a.C2;
+  const int BK = bf16 ? 64 : 32;  // conv_pipe's K-chunk: 128 B of channels
   const bool pipe = a.zero && Cin % BK == 0 && a.C1 % BK == 0 && a.K == a.ksize * a.ksize * Cin;
-  const int v = g_conv_variant;
   const bool lin = !(a.upsample | a.zins);
+  const int nK = a.ksize * a.ksize * (Cin / BK);
+  // the K slices of `blocks` 128 x 128 tiles that the partial-tile workspace holds
+  auto fit = [&a](int S, int blocks) {
+    while (S > 1 && (long long)blocks * S * 16384 > a.splitk_cap) --S;
+    return S < 1 ? 1 : S;
+  };
   if (a.subpix) {
     if (!pipe || !lin || (a.subpix == 2 ? (a.ksize != 3 && !(a.ksize == 1 && a.Hout * a.Wout == 1)) : a.ksize != 2) ||
-        ((a.Hout * a.Wout) % 128 && 128 % (a.Hout * a.Wout)))
-      return hipErrorInvalidValue;
-    if constexpr (sizeof(T) == 2) {
-      if (conv_p4_sub_selected(a)) {  // 4 phases x pixel tiles x cout tiles, persistent
-        const dim3 gp(std::min(4 * (a.M / GNW_BN) * (a.Cout / CONV_BM), g_num_cus));
-        if (a.subpix == 1) {
-          if (a.Wout == 32) ITSD_LAUNCH((conv3x3_gn_p4_kernel<32, 128>), gp, dim3(512), 0, s, a);
-          else if (a.Wout == 16) ITSD_LAUNCH((conv3x3_gn_p4_kernel<16, 128>), gp, dim3(512), 0, s, a);
-          else ITSD_LAUNCH((conv3x3_gn_p4_kernel<8, 128>), gp, dim3(512), 0, s, a);
-        } else {
-          if (a.Wout == 32) ITSD_LAUNCH((conv3x3_gn_p4_kernel<32, 384>), gp, dim3(512), 0, s, a);
-          else if (a.Wout == 16) ITSD_LAUNCH((conv3x3_gn_p4_kernel<16, 384>), gp, dim3(512), 0, s, a);
-          else ITSD_LAUNCH((conv3x3_gn_p4_kernel<8, 384>), gp, dim3(512), 0, s, a);
-        }
-        return hipGetLastError();
-      }
+        ((a.Hout * a.Wout) % 128 && 128 % (a.Hout * a.Wout))) {
+      p.valid = false;
+      return p;
     }
-    grid.z = 4;
+    // 4 phases x pixel tiles x cout tiles, persistent
+    if (bf16 && p4_sub_selected(a)) return persistent(a.subpix == 1 ? ConvKernel::P4_SUB : ConvKernel::P4_CONVT, 4 * tiles256);
     // under-filled grids (the 4x4 -> 8x8 upsample at small batches, the CFG ConvTranspose2d from the 2x2
     // grid: 32-64 blocks): split K with the in-launch combine, the tiles' tickets per (phase, tile)
-    if (a.splitk_ws && a.tickets && g_splitk && g_splitk_inl && g_subpix_split) {
-      const int blocks = (int)(grid.x * grid.y) * 4;
-      const int nK = a.ksize * a.ksize * (Cin / BK);
-      int S = 1;
-      if (blocks < 256 && blocks <= kTicketCap) S = std::min((512 + blocks - 1) / blocks, nK / 8);
-      while (S > 1 && (long long)blocks * S * 16384 > a.splitk_cap) --S;
-      if (S > 1) grid.z = 4 * S;
-    }
-    // (3- / 4-stage rings at one block a CU measured 8-30 % slower here and were removed in round 5,
-    // profiles/r04/census_archC_2N64_conv_variant*.txt)
-    ITSD_LAUNCH((conv_pipe<T, 2, true>), grid, dim3(256), 0, s, a);
-    return hipGetLastError();
+    const int blocks = (int)(grid.x * grid.y) * 4;
+    if (a.splitk_ws && a.tickets && g_splitk && g_splitk_inl && g_subpix_split && blocks < 256 && blocks <= kTicketCap)
+      p.S = fit(std::min((512 + blocks - 1) / blocks, nK / 8), blocks);
+    p.kernel = ConvKernel::PIPE_SUBPIX;
+    p.grid = dim3(grid.x, grid.y, 4 * p.S);
+    return p;
   }
-  ConvArgs b = a;  // (conv_pipe's split-K: in-launch combine unless the tiles outnumber the tickets)
-  if (pipe && v != 1 && a.splitk_ws && g_splitk) {
+  p.grid = grid;
+  if (!pipe || g_conv_variant == 1) return p;  // (conv_igemm)
+  p.kernel = lin ? ConvKernel::PIPE_LIN : ConvKernel::PIPE;
+  if (a.splitk_ws && g_splitk) {
     // under-filled grids (the 8x8 / 4x4 levels): split K so that >= ~2 blocks per CU exist,
-    // keeping >= 8 K-stages per slice
+    // keeping >= 8 K-stages per slice; in-launch combine unless the tiles outnumber the tickets
     const int blocks = (int)(grid.x * grid.y);
-    if (blocks > kTicketCap || !g_splitk_inl) b.tickets = nullptr;
-    const int nK = a.ksize * a.ksize * (Cin / BK);
+    p.inl = blocks <= kTicketCap && g_splitk_inl;
     int S = 1;
     if (g_splitk >= 2) S = std::min(g_splitk, nK / 4);  // forced slice count (measurements)
     else if (blocks < 256) S = std::min((512 + blocks - 1) / blocks, nK / 8);  // measured: helps only < 1 block/CU
-    while (S > 1 && (long long)blocks * S * 16384 > a.splitk_cap) --S;
-    grid.z = S < 1 ? 1 : S;
+    p.S = fit(S, blocks);
+    p.grid.z = p.S;
+    p.epilogue = p.S > 1 && !(p.inl && a.tickets);
   }
-  if (!pipe || v == 1) ITSD_LAUNCH(conv_igemm<T>, grid, dim3(256), 0, s, a);
-  else if (lin) ITSD_LAUNCH((conv_pipe<T, 2, true>), grid, dim3(256), 0, s, b);
-  else ITSD_LAUNCH((conv_pipe<T, 2, false>), grid, dim3(256), 0, s, b);
-  if (grid.z > 1 && pipe && v != 1 && !b.tickets) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    ITSD_LAUNCH(splitk_epilogue_kernel<T>, dim3(grid.x, grid.y), dim3(256), 0, s, a, (int)grid.z);
+  return p;
+}
+
+#ifdef ITSD_DIAG
+// Diagnostic builds: the compile-time ablations of conv3x3_gn_p4_kernel<32> (conv_dbg 4096 | AB << 13)
+static hipError_t launch_p4_ablation(const ConvArgs& a, dim3 gp, hipStream_t s) {
+  switch ((g_conv_dbg >> 13) & 127) {
+    case 2: ITSD_LAUNCH((conv3x3_gn_p4_kernel<32, 2>), gp, dim3(512), 0, s, a); break;
+    case 4: ITSD_LAUNCH((conv3x3_gn_p4_kernel<32, 4>), gp, dim3(512), 0, s, a); break;
+    case 8: ITSD_LAUNCH((conv3x3_gn_p4_kernel<32, 8>), gp, dim3(512), 0, s, a); break;
+    case 16: ITSD_LAUNCH((conv3x3_gn_p4_kernel<32, 16>), gp, dim3(512), 0, s, a); break;
+    case 24: ITSD_LAUNCH((conv3x3_gn_p4_kernel<32, 24>), gp, dim3(512), 0, s, a); break;
+    case 10: ITSD_LAUNCH((conv3x3_gn_p4_kernel<32, 10>), gp, dim3(512), 0, s, a); break;
+    case 32: ITSD_LAUNCH((conv3x3_gn_p4_kernel<32, 32>), gp, dim3(512), 0, s, a); break;
+    case 64: ITSD_LAUNCH((conv3x3_gn_p4_kernel<32, 64>), gp, dim3(512), 0, s, a); break;
+    case 18: ITSD_LAUNCH((conv3x3_gn_p4_kernel<32, 18>), gp, dim3(512), 0, s, a); break;
+    default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }
 
-template hipError_t launch_conv<float>(const ConvArgs&, hipStream_t);
-template hipError_t launch_conv<bf16_t>(const ConvArgs&, hipStream_t);
+#endif
+
+// Every kernel expression is spelled out at its launch: ITSD_LAUNCH records its text as the census name.
+#define ITSD_GO(K) ITSD_LAUNCH(K, p.grid, dim3(p.block), 0, s, a)
+#define ITSD_GO_W(K32, K16, K8)    \
+  do {                             \
+    if (a.Wout == 32) ITSD_GO(K32); \
+    else if (a.Wout == 16) ITSD_GO(K16); \
+    else ITSD_GO(K8);              \
+  } while (0)
+
+static void launch_p5(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+  if (p.kernel == ConvKernel::P5_SHARED) {
+    if (a.Wout == 4) ITSD_GO((conv3x3_gn_p5_kernel<4, 128, true>));
+    else ITSD_GO_W((conv3x3_gn_p5_kernel<32, 128, true>), (conv3x3_gn_p5_kernel<16, 128, true>), (conv3x3_gn_p5_kernel<8, 128, true>));
+    return;
+  }
+  if (a.Wout == 64) ITSD_GO(conv3x3_gn_p5_kernel<64>);
+#ifdef ITSD_DIAG
+  else if (a.Wout == 8 && p.cb == 64) ITSD_GO((conv3x3_gn_p5_kernel<8, 64>));
+  else if (a.Wout <= 8 && p.cb == 64) ITSD_GO((conv3x3_gn_p5_kernel<4, 64>));
+#endif
+  else if (a.Wout == 4) ITSD_GO(conv3x3_gn_p5_kernel<4>);
+  else ITSD_GO_W(conv3x3_gn_p5_kernel<32>, conv3x3_gn_p5_kernel<16>, conv3x3_gn_p5_kernel<8>);
+}
+
+static void launch_stream1x1(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+  const int Cin = a.C1 + a.C2;
+#define ITSD_S1(NS)                                                 \
+  if (Cin == 128) ITSD_GO((conv1x1_stream_kernel<128, NS>));        \
+  else if (Cin == 256) ITSD_GO((conv1x1_stream_kernel<256, NS>));   \
+  else if (Cin == 384) ITSD_GO((conv1x1_stream_kernel<384, NS>));   \
+  else if (Cin == 512) ITSD_GO((conv1x1_stream_kernel<512, NS>));   \
+  else ITSD_GO((conv1x1_stream_kernel<640, NS>));
+  if (g_conv1x1 == 2) {
+    ITSD_S1(7)
+  } else {
+    ITSD_S1(4)
+  }
+#undef ITSD_S1
+}
+
+// Runs the plan plan_conv made for these arguments (api.hip resolves both once per pass).
+template <typename T>
+hipError_t launch_conv(const ConvArgs& a0, const ConvPlan& p, hipStream_t s) {
+  // (arguments and plan belong together: the consumer GroupNorm's output is written by conv_small's epilogue only,
+  // a shortcut rides on p5's K slices only; the bf16 kernels take bf16 tensors)
+  const bool generic = p.kernel == ConvKernel::PIPE_LIN || p.kernel == ConvKernel::PIPE ||
+                       p.kernel == ConvKernel::PIPE_SUBPIX || p.kernel == ConvKernel::IGEMM;
+  if (!p.valid || (a0.gn_out && p.kernel != ConvKernel::SMALL) || (a0.sc_C1 + a0.sc_C2 && !p.sc_split) ||
+      (sizeof(T) != 2 && !generic))
+    return hipErrorInvalidValue;
+  ConvArgs a = a0;
+  switch (p.kernel) {
+    case ConvKernel::P5:
+    case ConvKernel::P5_SHARED:
+      a.ksplit = p.ksplit;
+      a.sc_split = p.sc_split;
+      a.kdist = p.kdist;
+      a.kpub = p.kpub;
+      a.kxl = p.kxl;
+      launch_p5(a, p, s);
+      break;
+    case ConvKernel::P4_GN:
+#ifdef ITSD_DIAG
+      if ((g_conv_dbg & 4096) && a.Wout == 32) return launch_p4_ablation(a, p.grid, s);
+#endif
+      ITSD_GO_W(conv3x3_gn_p4_kernel<32>, conv3x3_gn_p4_kernel<16>, conv3x3_gn_p4_kernel<8>);
+      break;
+    case ConvKernel::P4_C96: ITSD_GO((conv3x3_gn_p4_kernel<8, 512>)); break;
+    case ConvKernel::P4_PLAIN:
+      ITSD_GO_W((conv3x3_gn_p4_kernel<32, 2>), (conv3x3_gn_p4_kernel<16, 2>), (conv3x3_gn_p4_kernel<8, 2>));
+      break;
+    case ConvKernel::P4_SUB:
+      ITSD_GO_W((conv3x3_gn_p4_kernel<32, 128>), (conv3x3_gn_p4_kernel<16, 128>), (conv3x3_gn_p4_kernel<8, 128>));
+      break;
+    case ConvKernel::P4_CONVT:
+      ITSD_GO_W((conv3x3_gn_p4_kernel<32, 384>), (conv3x3_gn_p4_kernel<16, 384>), (conv3x3_gn_p4_kernel<8, 384>));
+      break;
+    case ConvKernel::GN128:
+      if (p.gn_segs == 1) ITSD_GO(conv3x3_gn_kernel<1>);
+      else ITSD_GO(conv3x3_gn_kernel<2>);
+      break;
+    case ConvKernel::STREAM1X1: launch_stream1x1(a, p, s); break;
+    case ConvKernel::SMALL: ITSD_GO(conv_small<false>); break;
+    // (3- / 4-stage rings at one block a CU measured 8-30 % slower for the sub-pixel phases and were removed in
+    // round 5, profiles/r04/census_archC_2N64_conv_variant*.txt)
+    case ConvKernel::PIPE_SUBPIX: ITSD_GO((conv_pipe<T, 2, true>)); break;
+    case ConvKernel::PIPE_LIN:
+    case ConvKernel::PIPE:
+      if (!p.inl) a.tickets = nullptr;
+      if (p.kernel == ConvKernel::PIPE_LIN) ITSD_GO((conv_pipe<T, 2, true>));
+      else ITSD_GO((conv_pipe<T, 2, false>));
+      if (p.epilogue) {
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        ITSD_LAUNCH(splitk_epilogue_kernel<T>, dim3(p.grid.x, p.grid.y), dim3(256), 0, s, a0, (int)p.grid.z);
+      }
+      break;
+    case ConvKernel::IGEMM: ITSD_GO(conv_igemm<T>); break;
+  }
+  return hipGetLastError();
+}
+#undef ITSD_GO_W
+#undef ITSD_GO
+
+template hipError_t launch_conv<float>(const ConvArgs&, const ConvPlan&, hipStream_t);
+template hipError_t launch_conv<bf16_t>(const ConvArgs&, const ConvPlan&, hipStream_t);
 
 }  // namespace itsd
 

@@ -79,6 +79,12 @@ int main() {
   expect("set_option p5_dist=1", itsd_set_option("p5_dist", 1), ITSD_OK);
   expect("set_option p5_pub=2", itsd_set_option("p5_pub", 2), ITSD_ERR_INVALID);
   expect("set_option p5_pub=1", itsd_set_option("p5_pub", 1), ITSD_OK);
+  expect("set_option small_gn=2", itsd_set_option("small_gn", 2), ITSD_ERR_INVALID);
+  expect("set_option small_gn=0", itsd_set_option("small_gn", 0), ITSD_OK);
+  expect("set_option small_gn=1 (default)", itsd_set_option("small_gn", 1), ITSD_OK);
+  expect("set_option p5_xl=4", itsd_set_option("p5_xl", 4), ITSD_ERR_INVALID);
+  expect("set_option p5_xl=0", itsd_set_option("p5_xl", 0), ITSD_OK);
+  expect("set_option p5_xl=3 (default)", itsd_set_option("p5_xl", 3), ITSD_OK);
   expect("set_option conv_variant=3 (removed)", itsd_set_option("conv_variant", 3), ITSD_ERR_INVALID);
   expect("set_option conv_variant=2 (default)", itsd_set_option("conv_variant", 2), ITSD_OK);
   expect("set_option spin_bound=-1", itsd_set_option("spin_bound", -1), ITSD_ERR_INVALID);
