@@ -16,6 +16,10 @@
  *                                   (Diffusion/Diffusion.py:51-65, DiffusionCondition.py:57-73)
  *   itsd_sampler_run             <- GaussianDiffusionSampler.forward loop
  *                                   (Diffusion.py:84-102, DiffusionCondition.py:89-105)
+ *   itsd_sampler_predict_x0      <- (no reference counterpart) the x_0 estimate of a half-denoised state, what a
+ *                                   verifier can score mid-trajectory: the branching PathSearch its docstring
+ *                                   describes (search/search_algorithm.py:238-250; its code, :307-312, is a placeholder)
+ *   itsd_branch                  <- (no reference counterpart) gather the surviving paths and re-noise them
  *   itsd_verify                  <- OracleVerifier / SelfSupervisedVerifier /
  *                                   AestheticPredictor .score (search/verifier.py:45-66,
  *                                   223-248, 262-287), batched per candidate
@@ -119,6 +123,25 @@ int itsd_set_schedule(itsd_unet* u, int T, const float* coeff1, const float* coe
  * step t uses noise[t] (t >= 1; the reference draws no noise at t = 0). labels: CFG only. */
 int itsd_sampler_run(itsd_unet* u, float* x, const int32_t* labels, int n, int t_begin, int t_end,
                      uint64_t seed, int64_t noise_offset, const float* noise, uint32_t flags, void* stream);
+
+/* x0[n,3,H,W] = clip(a0*x - b0*eps(x, t[, labels]), -1, 1): the sampler's own forward at step t
+ * (guided for CFG) with the x0 epilogue; x is not modified. Needs itsd_set_schedule (t < T_sched).
+ * x is the state x_t, the INPUT of step t (what itsd_sampler_run(.., t_end = t + 1) leaves); the caller passes
+ * a0 = 1/sqrt(abar_t), b0 = sqrt(1/abar_t - 1) (fp64 on the host, cast). Runs eagerly: no step graph is captured or
+ * evicted, and the NaN flag of the last itsd_sampler_run is left alone. ITSD_ERR_INVALID before any HIP call: null
+ * u / x / x0, t outside [0, T_sched), CFG without labels, n outside [1, max_batch]. */
+int itsd_sampler_predict_x0(itsd_unet* u, const float* x, const int32_t* labels, int n, int t,
+                            float a0, float b0, float* x0, void* stream);
+
+/* dst[j][e] = a * src[parents[j]][e] + b * z,  z ~ N(0,1) from Philox keyed
+ * (seed, stream_id, (cand_offset + j) * per_cand + e) -- the same z itsd_noise draws for candidate
+ * cand_offset + j. j < n_dst, e < per_cand. parents: HOST int32[n_dst], each in [0, n_src).
+ * src [n_src][per_cand] and dst [n_dst][per_cand] are device fp32 and must not overlap. b == 0: no draw.
+ * The table is read during the call (it travels in the kernel arguments) and may be freed after it. A parent out of
+ * range, overlapping ranges, a null pointer, n_src < 1, n_dst < 0 or per_cand < 1: ITSD_ERR_INVALID before any HIP
+ * call. n_dst == 0: a no-op. */
+int itsd_branch(float* dst, const float* src, const int32_t* parents, int n_src, int n_dst, int64_t per_cand,
+                float a, float b, uint64_t seed, uint32_t stream_id, int64_t cand_offset, void* stream);
 
 /* out[c][e] = (pivot ? pivot[e] : 0) + scale * z, z ~ N(0,1) from Philox keyed
  * (seed, stream_id, (cand_offset + c) * per_cand + e), for c < n_cand, e < per_cand.

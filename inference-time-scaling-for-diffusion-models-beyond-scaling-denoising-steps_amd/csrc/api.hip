@@ -55,6 +55,8 @@ int g_io_mfma = 1;  // bf16 head / tail on MFMA (itsd_set_option "io_mfma", read
 int g_small_gn = 1;  // conv_small writes its consumer GroupNorm's output (itsd_set_option "small_gn"): 0 off, 1 on
 hipError_t launch_noise(float*, const float*, int, long long, float, unsigned long long, unsigned, long long,
                         hipStream_t);
+hipError_t launch_branch(float*, const float*, const int*, int, long long, float, float, unsigned long long, unsigned,
+                         long long, hipStream_t);
 template <typename T> hipError_t launch_nhwc_to_nchw(const void*, float*, int, int, int, hipStream_t);
 }  // namespace itsd
 
@@ -1630,6 +1632,59 @@ int itsd_sampler_run(itsd_unet* u, float* x, const int32_t* labels, int n, int t
     if (flag[1]) return fail(ITSD_ERR_HANDOFF, handoff_msg(flag[1]));
     if (flag[0]) return fail(ITSD_ERR_NAN, "nan in tensor.");
   }
+  return ITSD_OK;
+}
+
+// The x_0 estimate of the state x at step t: the sampler step's own program (the doubled cond||uncond batch for CFG,
+// the time-embedding row selected on the device through d_t) with the tail's x0 epilogue (TailArgs::step_mode 2).
+// Eager, on x itself: no step graph is captured, looked up or evicted, and the sampler's run parameters and NaN flag
+// stay as the last run left them.
+int itsd_sampler_predict_x0(itsd_unet* u, const float* x, const int32_t* labels, int n, int t, float a0, float b0,
+                            float* x0, void* stream) {
+  if (!u || !x || !x0) return fail(ITSD_ERR_INVALID, "null argument");
+  if (!u->T_sched) return fail(ITSD_ERR_INVALID, "itsd_set_schedule not called");
+  if (u->cfg && !labels) return fail(ITSD_ERR_INVALID, "CFG sampler needs labels");
+  CHK(check_batch(u, n));
+  if (t < 0 || t >= u->T_sched)
+    return fail(ITSD_ERR_INVALID, "step " + std::to_string(t) + " outside [0, T_sched=" + std::to_string(u->T_sched) + ")");
+  HIPCHK(hipSetDevice(u->device));
+  u->last_forward_n = 0;  // (the tail input is overwritten: itsd_unet_representation refuses until the next forward)
+  hipStream_t cs = (hipStream_t)stream;
+  hipStream_t s = u->stream;
+  HIPCHK(hipEventRecord(u->ev_in, cs));
+  HIPCHK(hipStreamWaitEvent(s, u->ev_in, 0));
+  RunCtx c{};
+  c.nb = u->cfg ? 2 * n : n;
+  c.x = x; c.x_mod = n;
+  c.temb = u->temb_table; c.tsel = u->d_t; c.temb_img_stride = 0;
+  c.labels = labels; c.label_mod = n; c.uncond_from = u->cfg ? n : -1;
+  TailArgs& ta = c.tail;
+  ta.n = n; ta.cfg = u->cfg ? 1 : 0; ta.guide_w = u->guide_w; ta.guide_w1 = u->guide_w1;
+  ta.step_mode = 2; ta.x = const_cast<float*>(x); ta.a0 = a0; ta.b0 = b0; ta.x0_out = x0;
+  HIPCHK(launch_set_int(u->d_t, t, s));
+  HIPCHK(hipMemsetAsync(u->d_nan + 1, 0, 4, s));  // this forward's hand-off status (itsd_unet_query "status")
+  CHK(run_program(u, c, resolve_program(u, c), s));
+  HIPCHK(hipEventRecord(u->ev_out, s));
+  HIPCHK(hipStreamWaitEvent(cs, u->ev_out, 0));
+  return ITSD_OK;
+}
+
+int itsd_branch(float* dst, const float* src, const int32_t* parents, int n_src, int n_dst, int64_t per_cand, float a,
+                float b, uint64_t seed, uint32_t stream_id, int64_t cand_offset, void* stream) {
+  if (!dst || !src || !parents) return fail(ITSD_ERR_INVALID, "itsd_branch: null argument");
+  if (n_src < 1 || n_dst < 0 || per_cand < 1)
+    return fail(ITSD_ERR_INVALID, "itsd_branch: needs n_src >= 1, n_dst >= 0, per_cand >= 1");
+  if (n_dst == 0) return ITSD_OK;
+  for (int j = 0; j < n_dst; ++j)
+    if (parents[j] < 0 || parents[j] >= n_src)
+      return fail(ITSD_ERR_INVALID, "itsd_branch: parents[" + std::to_string(j) + "] = " + std::to_string(parents[j]) +
+                                        " outside [0, n_src=" + std::to_string(n_src) + ")");
+  {
+    const uintptr_t d0 = (uintptr_t)dst, s0 = (uintptr_t)src;
+    const uintptr_t db = (uintptr_t)n_dst * (uintptr_t)per_cand * 4, sb = (uintptr_t)n_src * (uintptr_t)per_cand * 4;
+    if (d0 < s0 + sb && s0 < d0 + db) return fail(ITSD_ERR_INVALID, "itsd_branch: dst and src overlap");
+  }
+  HIPCHK(launch_branch(dst, src, parents, n_dst, per_cand, a, b, seed, stream_id, cand_offset, (hipStream_t)stream));
   return ITSD_OK;
 }
 

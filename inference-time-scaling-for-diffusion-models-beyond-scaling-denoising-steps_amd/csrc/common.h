@@ -319,7 +319,7 @@ struct TailArgs {
   float guide_w;        // w (fp32 cast of the Python float)
   float guide_w1;       // (1 + w) computed in double then cast, as the reference's scalar
   // mode
-  int step_mode;        // 0: write eps NCHW; 1: sampler update of x in place
+  int step_mode;        // 0: write eps NCHW; 1: sampler update of x in place; 2: x0_out = clip(a0 x - b0 eps) (x read only)
   float* eps_out;       // NCHW [n][3][H][W]
   float* x;             // NCHW [n][3][H][W]
   const int* tsel;      // current step t (device)
@@ -333,6 +333,11 @@ struct TailArgs {
   // (k = tap*C + ci; k-step ks, lane group kg, output channel, 8 consecutive k)
   const float* coef;
   const bf16_t* wmf;
+  // step_mode 2 (itsd_sampler_predict_x0): a0 = 1/sqrt(abar_t), b0 = sqrt(1/abar_t - 1) as fp32, output NCHW [n][3][H][W]
+  float a0, b0;
+  float* x0_out;
 };
+
+constexpr int kBranchChunk = 256;  // parent-table rows a branch_kernel launch carries in its arguments (1 KiB)
 
 }  // namespace itsd

@@ -1616,7 +1616,16 @@ __device__ __forceinline__ float philox_normal(unsigned long long seed, unsigned
 //   mean = coeff1[t]*x - coeff2[t]*eps ;  x = mean + sqrt(var[t]) * z  (z = 0 at t = 0)
 // CFG: eps = (1+w) eps_c - w eps_u (DiffusionCondition.py:85) with the unconditional
 // branch at image index img + n of g.
-template <typename T>
+// X0 (TailArgs::step_mode 2, its own instantiation: the eps / step kernels' code is what it was): the epilogue writes
+//   x0 = clip(a0 * x - b0 * eps, -1, 1)   (the x_0 estimate of the state x at this step, guided eps for CFG)
+// to x0_out; x is only read, no noise is drawn, the NaN flag is not touched, a.run and the schedule tables are not read.
+__device__ __forceinline__ float tail_x0(float a0, float b0, float xv, float e) {
+#pragma clang fp contract(off)
+  const float v = a0 * xv - b0 * e;
+  return fminf(fmaxf(v, -1.0f), 1.0f);
+}
+
+template <typename T, bool X0 = false>
 __global__ __launch_bounds__(256) void tail_kernel(TailArgs a) {
   constexpr int EPC = 16 / (int)sizeof(T);
   extern __shared__ __attribute__((aligned(16))) float wl[];  // [9][C][3]
@@ -1671,6 +1680,14 @@ __global__ __launch_bounds__(256) void tail_kernel(TailArgs a) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) eps[c] = w1 * eps[c] - a.guide_w * u[c];
   }
+  if constexpr (X0) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const size_t o = ((size_t)img * 3 + c) * HW + rem;
+      a.x0_out[o] = tail_x0(a.a0, a.b0, a.x[o], eps[c]);
+    }
+    return;
+  }
   if (!a.step_mode) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) a.eps_out[((size_t)img * 3 + c) * HW + rem] = eps[c];
@@ -1702,7 +1719,7 @@ __global__ __launch_bounds__(256) void tail_kernel(TailArgs a) {
 // Tiled tail: one block per 64 output pixels (64/W full rows of one image); the input
 // halo rows are staged once in LDS (coalesced 16-B loads, padded pixel stride: no bank
 // conflicts) and 4 threads per pixel split the channels, reduced by lane shuffles.
-template <typename T>
+template <typename T, bool X0 = false>
 __global__ __launch_bounds__(256) void tail2_kernel(TailArgs a) {
   constexpr int EPC = 16 / (int)sizeof(T);
   extern __shared__ __attribute__((aligned(16))) char tsm[];
@@ -1783,6 +1800,10 @@ __global__ __launch_bounds__(256) void tail2_kernel(TailArgs a) {
   }
   const int rem = (y0 + opx / W) * W + (opx - (opx / W) * W);
   const size_t o = ((size_t)img * 3 + oc) * HW + rem;
+  if constexpr (X0) {
+    a.x0_out[o] = tail_x0(a.a0, a.b0, a.x[o], e);
+    return;
+  }
   if (!a.step_mode) {
     a.eps_out[o] = e;
     return;
@@ -1824,7 +1845,7 @@ __global__ __launch_bounds__(256) void tail2_kernel(TailArgs a) {
 #endif
 __host__ __device__ constexpr int tail_pst(int C) { return 2 * C + (ITSD_TAIL_PAD32 ? 32 : 16); }
 
-template <int TM_PX, int NTH>
+template <int TM_PX, int NTH, bool X0 = false>
 __global__ __launch_bounds__(NTH, 2) void tail_mfma_kernel(TailArgs a) {
   constexpr int NW = NTH / 64, GPW = TM_PX / 16 / NW;  // waves; 16-pixel MFMA groups a wave
   static_assert(GPW >= 1 && GPW * 16 * NW == TM_PX, "tail geometry");
@@ -1855,7 +1876,14 @@ __global__ __launch_bounds__(NTH, 2) void tail_mfma_kernel(TailArgs a) {
   unsigned long long seedpre = 0;
   long long noffpre = 0;
   int clippre = -1;
-  if (a.step_mode) {
+  if constexpr (X0) {  // x only: the x0 epilogue reads neither a.run nor the schedule tables
+#pragma unroll
+    for (int k = 0; k < TIT; ++k) {
+      const int it = tid + NTH * k, opx = it < TM_PX * 3 ? it / 3 : 0, oc = it < TM_PX * 3 ? it - opx * 3 : 0;
+      const int rem = (y0 + opx / W) * W + (opx - (opx / W) * W);
+      xpre[k] = a.x[((size_t)img * 3 + oc) * HW + rem];
+    }
+  } else if (a.step_mode) {
     tpre = *a.tsel;
     seedpre = a.run->seed;
     noffpre = a.run->noise_offset;
@@ -1966,6 +1994,10 @@ __global__ __launch_bounds__(NTH, 2) void tail_mfma_kernel(TailArgs a) {
     }
     const int rem = (y0 + opx / W) * W + (opx - (opx / W) * W);
     const size_t o = ((size_t)img * 3 + oc) * HW + rem;
+    if constexpr (X0) {
+      a.x0_out[o] = tail_x0(a.a0, a.b0, xpre[k], e);
+      continue;
+    }
     if (!a.step_mode) {
       a.eps_out[o] = e;
       continue;
@@ -1999,38 +2031,49 @@ static bool tail_mfma_ok_px(int px, int H, int W, int C) {
 size_t tail_mfma_smem(int H, int W, int C) { return tail_mfma_smem_px(128, H, W, C); }
 bool tail_mfma_ok(int H, int W, int C) { return tail_mfma_ok_px(128, H, W, C); }
 
+// step_mode 2 needs its operands (and nothing of the step's)
+static bool tail_x0_ok(const TailArgs& a) { return a.step_mode != 2 || (a.x && a.x0_out); }
+
 hipError_t launch_tail_mfma(const TailArgs& a, hipStream_t s) {
-  if (!a.coef || !a.wmf || !tail_mfma_ok(a.H, a.W, a.C)) return hipErrorInvalidValue;
+  if (!a.coef || !a.wmf || !tail_mfma_ok(a.H, a.W, a.C) || !tail_x0_ok(a)) return hipErrorInvalidValue;
   static bool attr = false;
   if (!attr) {
-    for (const void* f : {(const void*)tail_mfma_kernel<128, 512>}) {
+    for (const void* f : {(const void*)tail_mfma_kernel<128, 512>, (const void*)tail_mfma_kernel<128, 512, true>}) {
       hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       if (e != hipSuccess) return e;
     }
     attr = true;
   }
-  ITSD_LAUNCH((tail_mfma_kernel<128, 512>), dim3(a.n * (a.H / (128 / a.W))), dim3(512),
-              tail_mfma_smem_px(128, a.H, a.W, a.C), s, a);
+  const dim3 grid(a.n * (a.H / (128 / a.W)));
+  const size_t sm = tail_mfma_smem_px(128, a.H, a.W, a.C);
+  if (a.step_mode == 2) ITSD_LAUNCH((tail_mfma_kernel<128, 512, true>), grid, dim3(512), sm, s, a);
+  else ITSD_LAUNCH((tail_mfma_kernel<128, 512>), grid, dim3(512), sm, s, a);
   return hipGetLastError();
 }
 
 template <typename T>
 hipError_t launch_tail(const TailArgs& a, hipStream_t s) {
+  if (!tail_x0_ok(a)) return hipErrorInvalidValue;
   if (a.W <= 64 && 64 % a.W == 0 && a.H % (64 / a.W) == 0 && a.C % 32 == 0) {
     const size_t sm = 27 * a.C * 4 + (size_t)(64 / a.W + 2) * (a.W + 2) * (a.C * sizeof(T) + 16) + 2 * 4 * 64 * 3 * 4;
     if (sm > 160 * 1024) return hipErrorInvalidValue;
     static bool attr = false;
     if (!attr) {
-      hipError_t e = hipFuncSetAttribute((const void*)tail2_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         160 * 1024);
-      if (e != hipSuccess) return e;
+      for (const void* f : {(const void*)tail2_kernel<T>, (const void*)tail2_kernel<T, true>}) {
+        hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) return e;
+      }
       attr = true;
     }
-    ITSD_LAUNCH(tail2_kernel<T>, dim3(a.n * (a.H / (64 / a.W))), dim3(256), sm, s, a);
+    const dim3 grid(a.n * (a.H / (64 / a.W)));
+    if (a.step_mode == 2) ITSD_LAUNCH((tail2_kernel<T, true>), grid, dim3(256), sm, s, a);
+    else ITSD_LAUNCH(tail2_kernel<T>, grid, dim3(256), sm, s, a);
     return hipGetLastError();
   }
   const long long total = (long long)a.n * a.H * a.W;
-  ITSD_LAUNCH(tail_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 27 * a.C * sizeof(float), s, a);
+  const dim3 grid((unsigned)((total + 255) / 256));
+  if (a.step_mode == 2) ITSD_LAUNCH((tail_kernel<T, true>), grid, dim3(256), 27 * a.C * sizeof(float), s, a);
+  else ITSD_LAUNCH(tail_kernel<T>, grid, dim3(256), 27 * a.C * sizeof(float), s, a);
   return hipGetLastError();
 }
 template hipError_t launch_tail<float>(const TailArgs&, hipStream_t);
@@ -2222,6 +2265,57 @@ hipError_t launch_noise(float* out, const float* pivot, int n_cand, long long pe
   ITSD_LAUNCH(noise_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, out, pivot, total, per_cand,
                      scale, seed, stream_id, cand_offset * per_cand);
   return hipGetLastError();
+}
+
+// dst[j][e] = a * src[parents[j]][e] + b * z(seed, stream_id, (cand0 + j) * per_cand + e): the gather-and-re-noise of a
+// path search's survivors (z is noise_kernel's draw for candidate cand0 + j). The parent table rides in the kernel
+// arguments (kBranchChunk rows a launch). grid = (element blocks, rows); VEC: 16-B loads and stores, 4 elements a
+// thread (per_cand % 4 == 0 and both bases 16-B aligned). b == 0: a scaled copy, no draw. 64-bit indices throughout.
+struct BranchParents { int p[kBranchChunk]; };
+template <bool VEC>
+__global__ __launch_bounds__(256) void branch_kernel(float* dst, const float* src, BranchParents par, long long per_cand,
+                                                     float a, float b, unsigned long long seed, unsigned stream_id,
+                                                     long long cand0) {
+  const long long j = blockIdx.y;
+  const float* sp = src + (long long)par.p[j] * per_cand;
+  float* dp = dst + j * per_cand;
+  const unsigned long long zb = (unsigned long long)(cand0 + j) * (unsigned long long)per_cand;
+  const long long stride = (long long)gridDim.x * 256;
+  if constexpr (VEC) {
+    const long long nv = per_cand >> 2;
+    for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < nv; v += stride) {
+      const f32x4 p4 = *(const f32x4*)(sp + 4 * v);
+      f32x4 o;
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        o[e] = b != 0.0f ? fmaf(a, p4[e], b * philox_normal(seed, stream_id, zb + (unsigned long long)(4 * v + e)))
+                         : a * p4[e];
+      *(f32x4*)(dp + 4 * v) = o;
+    }
+  } else {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < per_cand; i += stride)
+      dp[i] = b != 0.0f ? fmaf(a, sp[i], b * philox_normal(seed, stream_id, zb + (unsigned long long)i)) : a * sp[i];
+  }
+}
+// rows [0, n_dst) in chunks of kBranchChunk; parents is a HOST table, range-checked by the caller
+hipError_t launch_branch(float* dst, const float* src, const int* parents, int n_dst, long long per_cand, float a,
+                         float b, unsigned long long seed, unsigned stream_id, long long cand_offset, hipStream_t s) {
+  const bool vec = per_cand % 4 == 0 && ((uintptr_t)dst | (uintptr_t)src) % 16 == 0;
+  const long long items = vec ? per_cand / 4 : per_cand;
+  const unsigned gx = (unsigned)std::min<long long>((items + 255) / 256, 1 << 16);
+  for (int j0 = 0; j0 < n_dst; j0 += kBranchChunk) {
+    const int rows = std::min(kBranchChunk, n_dst - j0);
+    BranchParents par;
+    for (int j = 0; j < kBranchChunk; ++j) par.p[j] = j < rows ? parents[j0 + j] : 0;
+    float* d = dst + (long long)j0 * per_cand;
+    if (vec) ITSD_LAUNCH(branch_kernel<true>, dim3(gx, rows), dim3(256), 0, s, d, src, par, per_cand, a, b, seed,
+                         stream_id, cand_offset + j0);
+    else ITSD_LAUNCH(branch_kernel<false>, dim3(gx, rows), dim3(256), 0, s, d, src, par, per_cand, a, b, seed,
+                     stream_id, cand_offset + j0);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 // ============================================================================ representation

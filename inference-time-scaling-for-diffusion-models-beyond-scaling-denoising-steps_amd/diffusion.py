@@ -20,7 +20,7 @@ from typing import Optional, Sequence, Tuple
 
 import torch
 
-from .schedule import make_schedule
+from .schedule import make_schedule, x0_coeffs
 
 
 def _extract(v: torch.Tensor, t: torch.Tensor, ndim: int) -> torch.Tensor:
@@ -98,6 +98,22 @@ class GaussianDiffusionSampler:
         nat.run(x, t_begin, t_end, seed or 0, noise=noise, labels=labels, noise_offset=noise_offset, graph=graph,
                 clip=clip, sync=sync)
         return x
+
+    def predict_x0(self, x: torch.Tensor, t: int, labels: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The x_0 estimate of a half-denoised state: x is x_t, the input of step t (what ``run(.., t_end=t + 1)``
+        leaves); returns clip(x / sqrt(abar_t) - sqrt(1/abar_t - 1) eps(x, t), -1, 1) as a new tensor, with the eps
+        the sampler's step t would use (guided for the conditional sampler, which needs ``labels``). x is not
+        modified (``itsd_sampler_predict_x0``)."""
+        t = int(t)
+        if not 0 <= t < self.T:
+            raise ValueError(f"step {t} outside [0, T={self.T})")
+        x = x.to(self.model.device, torch.float32).contiguous()
+        if labels is not None:
+            labels = labels.flatten().to(x.device, torch.int32).contiguous()
+        a0, b0 = x0_coeffs(self.sched.alphas_bar, t)
+        out = torch.empty_like(x)
+        self._native(x.shape[0]).predict_x0(x, t, a0, b0, out, labels=labels)
+        return out
 
     def forward(self, x_T: torch.Tensor, noise: Optional[torch.Tensor] = None, seed: Optional[int] = None,
                 graph: bool = True) -> torch.Tensor:

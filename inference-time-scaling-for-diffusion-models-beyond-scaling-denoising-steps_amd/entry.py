@@ -413,8 +413,23 @@ def _search(cfg: Dict[str, Any], sampler, img_size: int, labels: Optional[torch.
                                                       float(s.get("lambda_radius", 0.95)),
                                                       int(s.get("n_iterations") or 10), labels=lab)
         elif algo == "path":
-            best, score, hist = eng.path_search(init, int(s.get("n_paths") or 4), float(s.get("noise_scale", 0.1)),
-                                                int(s.get("injection_step") or 400), labels=lab)
+            mode = (s.get("path_mode") or "placeholder").lower()
+            n_paths, inj = int(s.get("n_paths") or 4), s.get("injection_step") or 400
+            if mode == "branch":  # branch at injection_step (an int or a strictly decreasing list)
+                from .search import default_keep, injection_step_list
+
+                keep = s.get("keep")
+                best, score, hist = eng.path_search_branch(
+                    init, n_paths, float(s.get("noise_scale", 0.1)), [int(v) for v in injection_step_list(inj)],
+                    default_keep(n_paths) if keep is None else int(keep), int(s.get("renoise_steps") or 0),
+                    labels=lab)
+            elif mode == "placeholder":
+                if isinstance(inj, (list, tuple)):  # (recorded in the history only)
+                    inj = inj[0]
+                best, score, hist = eng.path_search(init, n_paths, float(s.get("noise_scale", 0.1)), int(inj),
+                                                    labels=lab)
+            else:
+                raise ValueError(f"unknown search.path_mode '{mode}' (placeholder | branch)")
         else:
             raise ValueError(f"unknown search.algorithm '{algo}'")
     # the winner's own denoised image: kept by its owner rank during the search and broadcast

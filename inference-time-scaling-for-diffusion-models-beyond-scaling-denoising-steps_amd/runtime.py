@@ -55,6 +55,11 @@ _SIGS = {
                           ctypes.c_float],
     "itsd_sampler_run": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                          ctypes.c_uint64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p],
+    "itsd_sampler_predict_x0": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                ctypes.c_float, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p],
+    "itsd_branch": [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.c_int,
+                    ctypes.c_int64, ctypes.c_float, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int64,
+                    ctypes.c_void_p],
     "itsd_noise": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_uint64,
                    ctypes.c_uint32, ctypes.c_int64, ctypes.c_void_p],
     "itsd_verify": [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
@@ -190,6 +195,14 @@ class NativeUNet:
                                      int(seed) & ((1 << 64) - 1), int(noise_offset), _ptr(noise), flags,
                                      stream_ptr(x.device)))
 
+    def predict_x0(self, x: torch.Tensor, t: int, a0: float, b0: float, out: torch.Tensor,
+                   labels: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """out = clip(a0 x - b0 eps(x, t[, labels]), -1, 1) with the sampler step's own eps; x is only read."""
+        assert out.shape == x.shape and out.dtype == torch.float32 and out.is_contiguous() and x.is_contiguous()
+        check(lib().itsd_sampler_predict_x0(self.h, x.data_ptr(), _ptr(labels), x.shape[0], int(t), float(a0),
+                                            float(b0), out.data_ptr(), stream_ptr(x.device)))
+        return out
+
     def query(self, key: str) -> int:
         """itsd_unet_query: "graph_captures", "max_batch", "T_sched", "ws_bytes", "ops"."""
         v = ctypes.c_int64()
@@ -247,6 +260,24 @@ def noise(out: torch.Tensor, n_cand: int, seed: int, stream_id: int, cand_offset
                            int(seed) & ((1 << 64) - 1), int(stream_id) & 0xFFFFFFFF, int(cand_offset),
                            stream_ptr(out.device)))
     return out
+
+
+def branch(dst: torch.Tensor, src: torch.Tensor, parents: Sequence[int], a: float, b: float, seed: int,
+           stream_id: int, cand_offset: int = 0) -> torch.Tensor:
+    """dst[j] = a * src[parents[j]] + b * z, z the draw ``noise`` makes for candidate cand_offset + j of
+    (seed, stream_id) (``itsd_branch``). src holds n_src candidates of dst.numel() / len(parents) elements each;
+    parents is a host sequence; dst and src must not overlap. b == 0: a scaled gather, no draw."""
+    n_dst = len(parents)
+    assert dst.dtype == torch.float32 and src.dtype == torch.float32 and dst.is_contiguous() and src.is_contiguous()
+    if n_dst == 0:
+        return dst
+    per = dst.numel() // n_dst
+    assert per * n_dst == dst.numel() and per > 0 and src.numel() % per == 0, "dst / src do not split into candidates"
+    tab = (ctypes.c_int32 * n_dst)(*[int(p) for p in parents])
+    check(lib().itsd_branch(dst.data_ptr(), src.data_ptr(), tab, src.numel() // per, n_dst, per, float(a), float(b),
+                            int(seed) & ((1 << 64) - 1), int(stream_id) & 0xFFFFFFFF, int(cand_offset),
+                            stream_ptr(dst.device)))
+    return dst
 
 
 CALIB_MFMA_BF16, CALIB_HBM_COPY, CALIB_MFMA_BF16_16X16 = 0, 1, 2

@@ -12,6 +12,8 @@ is precomputed here bit-for-bit with torch.
 from __future__ import annotations
 
 import dataclasses
+import math
+from typing import Tuple
 
 import torch
 import torch.nn.functional as F
@@ -27,6 +29,7 @@ class Schedule:
     coeff2: torch.Tensor         # fp64 [T]
     posterior_var: torch.Tensor  # fp64 [T]
     var: torch.Tensor            # fp64 [T]  (cat([posterior_var[1:2], betas[1:]]))
+    alphas_bar: torch.Tensor = None  # fp64 [T]  (cumprod(1 - betas); the x_0 estimate and re-noising read it)
 
     @property
     def coeff1_f32(self) -> torch.Tensor:
@@ -50,4 +53,20 @@ def make_schedule(beta_1: float, beta_T: float, T: int) -> Schedule:
     coeff2 = coeff1 * (1.0 - alphas) / torch.sqrt(1.0 - alphas_bar)
     posterior_var = betas * (1.0 - alphas_bar_prev) / (1.0 - alphas_bar)
     var = torch.cat([posterior_var[1:2], betas[1:]])
-    return Schedule(T, float(beta_1), float(beta_T), betas, coeff1, coeff2, posterior_var, var)
+    return Schedule(T, float(beta_1), float(beta_T), betas, coeff1, coeff2, posterior_var, var, alphas_bar)
+
+
+def x0_coeffs(alphas_bar: torch.Tensor, s: int) -> Tuple[float, float]:
+    """(a0, b0) of x0_hat = clip(a0 x_s - b0 eps(x_s, s)): a0 = 1/sqrt(abar_s), b0 = sqrt(1/abar_s - 1), computed in
+    fp64 (the device consumes their fp32 casts)."""
+    ab = float(alphas_bar[int(s)].double())
+    return 1.0 / math.sqrt(ab), math.sqrt(1.0 / ab - 1.0)
+
+
+def renoise_coeffs(alphas_bar: torch.Tensor, s: int, delta: int) -> Tuple[float, float]:
+    """(a, b) of x_{s+delta} = a x_s + b z, the forward process from step s to s + delta: r = abar_{s+delta} / abar_s,
+    a = sqrt(r), b = sqrt(1 - r) in fp64. delta = 0: (1, 0), a pure copy."""
+    if delta == 0:
+        return 1.0, 0.0
+    r = float(alphas_bar[int(s) + int(delta)].double()) / float(alphas_bar[int(s)].double())
+    return math.sqrt(r), math.sqrt(1.0 - r)

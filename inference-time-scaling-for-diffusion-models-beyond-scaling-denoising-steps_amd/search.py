@@ -35,10 +35,13 @@ import torch
 import torch.distributed as dist
 
 from . import runtime as rt
+from .schedule import renoise_coeffs
 
 _STREAM_XT = 0xF0000000      # Philox stream ids (the sampler uses stream id = t < T)
 _STREAM_PERTURB = 0xE0000000
 _STREAM_INIT = 0xD0000000    # the initial pivot of zero-order / path search
+_STREAM_BRANCH = 0xC0000000  # + stage index: the re-noising draws of a branching path search
+_ROUND_BRANCH = 0x5B000000   # + window index (>= 1): the sampler keys of the windows after a branch
 
 
 def strict_argmax(scores: torch.Tensor) -> Tuple[int, float]:
@@ -50,6 +53,33 @@ def strict_argmax(scores: torch.Tensor) -> Tuple[int, float]:
         return -1, float("-inf")
     i = int(torch.argmax(sc).item())  # first occurrence of the maximum
     return i, float(sc[i])
+
+
+def rank_desc(scores: torch.Tensor) -> List[int]:
+    """Indices by descending score: ``strict_argmax``'s order, extended to a full ranking. Ties go to the lower
+    index and a NaN counts as -inf (so NaNs come last, in index order)."""
+    sc = torch.as_tensor(scores).detach().double().cpu().flatten()
+    sc = torch.where(torch.isnan(sc), torch.full_like(sc, float("-inf")), sc).tolist()  # (+-inf stay themselves)
+    return sorted(range(len(sc)), key=lambda i: (-sc[i], i))
+
+
+def branch_parents(scores: torch.Tensor, keep: int) -> List[int]:
+    """The parent table of one branching stage over N = len(scores) paths: the ``keep`` best survive
+    (``rank_desc``) and each gets N // keep children, parents[j] = order[j // (N // keep)]."""
+    n = int(torch.as_tensor(scores).numel())
+    if keep < 1 or n % keep:
+        raise ValueError(f"keep={keep} must divide the {n} paths")
+    order, m = rank_desc(scores), n // keep
+    return [order[j // m] for j in range(n)]
+
+
+def root_of(parents: Sequence[Sequence[int]], index: int) -> int:
+    """Follow a final path index back through the stages' (global) parent tables to its initial candidate."""
+    for tab in reversed(list(parents)):
+        if index < 0:
+            break
+        index = tab[index]
+    return index
 
 
 # --------------------------------------------------------------------------- engine
@@ -277,8 +307,114 @@ class SearchEngine:
         return best, r.best_score, {"scores": r.scores.tolist(), "injection_points": [injection_step] * n_paths,
                                     "best_index": r.best_index}
 
+    # --- path search that branches at the injection steps
+    def window_key(self, i: int, renoise_steps: int = 0) -> int:
+        """The sampler's Philox key of window i of a branching path search. Window 0 (up to the first branch) keeps
+        the placeholder round's key, so the pre-branch trajectory is the placeholder's own. With renoise_steps > 0 a
+        later window re-runs steps s + renoise_steps .. s + 1, and takes a key of its own, derived from (seed, i):
+        under the old key those steps would replay, for the same position, the noise they drew before the branch.
+        With renoise_steps == 0 no step is ever run twice, every (key, step, position) draw is still unused, and the
+        key stays: a stage that changes nothing (every path its own only child) is then the placeholder bit for bit."""
+        fresh = i > 0 and renoise_steps > 0
+        return (self.seed * 1000003 + (_ROUND_BRANCH + i if fresh else 0)) & ((1 << 62) - 1)
+
+    def branch_latents(self, dst: torch.Tensor, src: torch.Tensor, parents: Sequence[int], a: float, b: float,
+                       stage: int, cand_offset: int) -> torch.Tensor:
+        """dst[j] = a src[parents[j]] + b z(seed, stage, global child index) on the device (``itsd_branch``)."""
+        return rt.branch(dst, src, parents, a, b, self.seed, _STREAM_BRANCH + stage, cand_offset=cand_offset)
+
+    def _gather(self, local: torch.Tensor) -> torch.Tensor:
+        parts = [torch.empty_like(local) for _ in range(self.world)]
+        dist.all_gather(parts, local.contiguous(), group=self.group)
+        return torch.cat(parts)
+
+    def path_search_branch(self, initial_noise: torch.Tensor, n_paths: int, noise_scale: float,
+                           injection_steps: Sequence[int], keep: int, renoise_steps: int = 0, labels=None):
+        """Path search that branches at intermediate steps (the reference's ``PathSearch`` docstring; its code is the
+        placeholder ``path_search`` keeps). N = n_paths paths start as the placeholder's candidates. At each
+        injection step s (strictly decreasing, 1 <= s, s + renoise_steps <= T - 1) every path is denoised down to
+        x_s, its x_0 estimate is scored, the ``keep`` best survive with N // keep children each, and the children are
+        the survivor re-noised ``renoise_steps`` steps up (0: a copy; they then diverge through the sampler's own
+        per-step noise, which is keyed by position). After the last stage the paths are denoised to the end and scored
+        as in ``path_search``.
+
+        Returns (best_noise, best_score, hist). best_noise is the initial noise of the winner's ROOT ancestor;
+        re-denoising it does NOT reproduce the winner, because the branch draws and the per-window sampler keys are
+        part of the path -- the winning image is ``self.best_image``. hist: ``scores`` (final, N), ``stage_scores``
+        [m][N], ``parents`` [m][N] (global indices), ``injection_points``, ``best_index``, ``root_index`` and
+        ``unet_steps`` = N x (sampler steps run + one x_0 evaluation per stage), a guided pair counting once."""
+        T = int(self.sampler.T)
+        steps = [int(s) for s in injection_steps] if isinstance(injection_steps, (list, tuple)) else None
+        if not steps or any(int(s) != s for s in injection_steps):
+            raise ValueError("injection_steps must be a non-empty list of ints")
+        delta, keep = int(renoise_steps), int(keep)
+        if delta < 0:
+            raise ValueError("renoise_steps must be >= 0")
+        if any(b >= a for a, b in zip(steps, steps[1:])):
+            raise ValueError(f"injection_steps {steps} must be strictly decreasing")
+        if steps[-1] < 1 or steps[0] + delta > T - 1:
+            raise ValueError(f"every injection step s needs 1 <= s and s + renoise_steps <= T - 1 = {T - 1}")
+        if keep < 1 or n_paths % keep:
+            raise ValueError(f"keep={keep} must divide n_paths={n_paths}")
+        if self.noise == "reference":
+            raise ValueError("the branching path search draws from Philox; noise='reference' covers the placeholder")
+        shape = tuple(initial_noise.shape)
+        self.best_image, self._best_owner = None, -1
+        self.reserve(n_paths, shape)
+        g0, nl = self.shard(n_paths)
+        per = int(torch.Size(shape).numel())
+        lab = None if labels is None else labels.to(self.device).flatten().repeat(nl)
+        pivot = initial_noise.to(self.device, torch.float32).contiguous()
+        x = self.candidate_noise(0, g0, nl, shape, pivot, noise_scale)  # round 0: the placeholder's candidates
+        abar = self.sampler.sched.alphas_bar
+        t_hi, ran = T - 1, 0
+        stage_scores, parents = [], []
+        for i, s in enumerate(steps):
+            if t_hi > s:  # steps t_hi .. s + 1: x becomes x_s
+                self.sampler.run(x, t_begin=t_hi, t_end=s + 1, labels=lab, seed=self.window_key(i, delta),
+                                 noise_offset=g0 * per, graph=self.graph, clip=False)
+                ran += t_hi - s
+            local = self.verifier.score_batch(self.sampler.predict_x0(x, s, labels=lab), nl)
+            sc = (self._gather(local) if self.dist else local).cpu()  # first collective of the stage
+            src = self._gather(x) if self.world > 1 else x            # second: every rank holds all N latents
+            tab = branch_parents(sc, keep)
+            a, b = renoise_coeffs(abar, s, delta)
+            x = self.branch_latents(torch.empty_like(x), src, tab[g0:g0 + nl], a, b, i, g0)
+            stage_scores.append(sc.tolist())
+            parents.append(tab)
+            t_hi = s + delta
+        self.sampler.run(x, t_begin=t_hi, t_end=0, labels=lab, seed=self.window_key(len(steps), delta),
+                         noise_offset=g0 * per, graph=self.graph, clip=True)
+        ran += t_hi + 1
+        local = self.verifier.score_batch(x, nl)
+        self.nfes += n_paths
+        sc = (self._gather(local) if self.dist else local).cpu()
+        best_index, best_score = strict_argmax(sc)
+        root = root_of(parents, best_index)
+        best = pivot.clone()  # (kept when no path beats -inf, as the placeholder)
+        if best_index >= 0:
+            best = self.candidate_noise(0, root, 1, shape, pivot=pivot, scale=noise_scale)
+            self._keep_best_image(RoundResult(sc, best_index, best_score, x, g0), shape)
+        self._publish_best_image(shape)
+        return best, best_score, {"scores": sc.tolist(), "stage_scores": stage_scores, "parents": parents,
+                                  "injection_points": steps, "best_index": best_index, "root_index": root,
+                                  "unet_steps": n_paths * (ran + len(steps))}
+
 
 # --------------------------------------------------------------------------- reference API
+def injection_step_list(injection_step) -> List[int]:
+    """``injection_step`` as the list a branching search takes: an int is one stage."""
+    return list(injection_step) if isinstance(injection_step, (list, tuple)) else [injection_step]
+
+
+def default_keep(n_paths: int) -> int:
+    """Survivors a branching stage keeps by default: max(1, n_paths // 4), rounded down to a divisor of n_paths."""
+    k = max(1, int(n_paths) // 4)
+    while n_paths % k:
+        k -= 1
+    return k
+
+
 def _iter(n, verbose, desc):
     if verbose:
         try:
@@ -374,18 +510,39 @@ class ZeroOrderSearch:
 
 class PathSearch:
     """``search_algorithm.py:238-340`` (the reference's injection is a placeholder:
-    each path denoises ``initial + noise_scale * randn`` from T)."""
+    each path denoises ``initial + noise_scale * randn`` from T). ``mode="branch"`` is the opt-in search that
+    branches at ``injection_step`` for real (``SearchEngine.path_search_branch``)."""
 
-    def __init__(self, n_paths: int = 4, injection_step: int = 400, noise_scale: float = 0.1, verbose: bool = False):
+    def __init__(self, n_paths: int = 4, injection_step=400, noise_scale: float = 0.1, verbose: bool = False, *,
+                 mode: str = "placeholder", keep: Optional[int] = None, renoise_steps: int = 0):
+        """mode="branch" (batched searches only): branch at ``injection_step`` (an int or a strictly decreasing
+        list) through ``SearchEngine.path_search_branch``; ``keep`` survivors a stage (default
+        ``default_keep(n_paths)``), re-noised ``renoise_steps`` steps up."""
+        if mode not in ("placeholder", "branch"):
+            raise ValueError("mode must be 'placeholder' (the reference's behaviour) or 'branch'")
         self.n_paths = n_paths
         self.injection_step = injection_step
         self.noise_scale = noise_scale
         self.verbose = verbose
+        self.mode = mode
+        self.keep = keep
+        self.renoise_steps = renoise_steps
         self.nfes = 0
 
     def search(self, initial_noise: torch.Tensor, denoise_fn: Callable, verifier_fn: Callable, timesteps: int = 1000,
                device: str = "cuda", verbose: Optional[bool] = None, batched: bool = False, sampler=None,
                seed: int = 0, reference_rng: bool = False, **kwargs):
+        if self.mode == "branch":
+            if not batched:
+                raise ValueError("PathSearch(mode='branch') needs batched=True: an opaque denoise_fn cannot be "
+                                 "stopped mid-trajectory")
+            eng = _engine(sampler, verifier_fn, seed, reference_rng)
+            out = eng.path_search_branch(initial_noise, self.n_paths, self.noise_scale,
+                                         injection_step_list(self.injection_step),
+                                         default_keep(self.n_paths) if self.keep is None else self.keep,
+                                         self.renoise_steps)
+            self.nfes += self.n_paths
+            return out
         if batched:
             eng = _engine(sampler, verifier_fn, seed, reference_rng)
             out = eng.path_search(initial_noise, self.n_paths, self.noise_scale, self.injection_step)
