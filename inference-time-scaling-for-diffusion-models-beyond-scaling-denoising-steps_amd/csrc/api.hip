@@ -1030,38 +1030,33 @@ std::vector<ConvLaunch> resolve_program(itsd_unet* u, const RunCtx& c) {
   return r;
 }
 
+// What both GroupNorm op kinds read: the (concatenated) input's channels, its statistics slabs, gamma / beta.
+GNArgs gn_args(const itsd_unet* u, const Op& o) {
+  GNArgs g{};
+  g.C1 = u->acts[o.src1].C;
+  g.C2 = o.src2 >= 0 ? u->acts[o.src2].C : 0;
+  g.HW = u->acts[o.src1].H * u->acts[o.src1].W;
+  g.gamma = u->wp(o.gamma);
+  g.beta = u->wp(o.beta);
+  g.eps = kGnEps;
+  g.st1 = (const float*)(u->ws + u->acts[o.src1].stats);
+  g.st2 = o.src2 >= 0 ? (const float*)(u->ws + u->acts[o.src2].stats) : nullptr;
+  g.spi1 = u->acts[o.src1].spi;
+  g.spi2 = o.src2 >= 0 ? u->acts[o.src2].spi : 0;
+  return g;
+}
+
 // cl: the op's resolved entry (conv ops)
 int launch_op(itsd_unet* u, const Op& o, const RunCtx& c, const ConvLaunch* cl, hipStream_t s) {
   hipError_t e = hipSuccess;
   if (o.kind == OP_GNCOEF) {
-    GNArgs g{};
-    g.C1 = u->acts[o.src1].C;
-    g.C2 = o.src2 >= 0 ? u->acts[o.src2].C : 0;
-    g.HW = u->acts[o.src1].H * u->acts[o.src1].W;
-    g.gamma = u->wp(o.gamma);
-    g.beta = u->wp(o.beta);
-    g.eps = kGnEps;
-    g.st1 = (const float*)(u->ws + u->acts[o.src1].stats);
-    g.st2 = o.src2 >= 0 ? (const float*)(u->ws + u->acts[o.src2].stats) : nullptr;
-    g.spi1 = u->acts[o.src1].spi;
-    g.spi2 = o.src2 >= 0 ? u->acts[o.src2].spi : 0;
-    e = launch_gn_coef(g, c.nb, (float*)(u->ws + o.coef), s);
+    e = launch_gn_coef(gn_args(u, o), c.nb, (float*)(u->ws + o.coef), s);
   } else if (o.kind == OP_GN) {
-    GNArgs a{};
+    GNArgs a = gn_args(u, o);
     a.src1 = u->ap(o.src1);
     a.src2 = o.src2 >= 0 ? u->ap(o.src2) : nullptr;
-    a.C1 = u->acts[o.src1].C;
-    a.C2 = o.src2 >= 0 ? u->acts[o.src2].C : 0;
-    a.HW = u->acts[o.src1].H * u->acts[o.src1].W;
-    a.gamma = u->wp(o.gamma);
-    a.beta = u->wp(o.beta);
-    a.eps = kGnEps;
     a.silu = o.silu;
     a.dst = u->ap(o.dst);
-    a.st1 = (const float*)(u->ws + u->acts[o.src1].stats);
-    a.st2 = o.src2 >= 0 ? (const float*)(u->ws + u->acts[o.src2].stats) : nullptr;
-    a.spi1 = u->acts[o.src1].spi;
-    a.spi2 = o.src2 >= 0 ? u->acts[o.src2].spi : 0;
     e = u->bf16 ? launch_groupnorm<bf16_t>(a, c.nb, s) : launch_groupnorm<float>(a, c.nb, s);
   } else if (o.kind == OP_CONV) {
     if (cl->rc != ITSD_OK) return fail(cl->rc, cl->err);
@@ -1128,7 +1123,10 @@ int run_program(itsd_unet* u, const RunCtx& c, const std::vector<ConvLaunch>& rp
     if (c.ev_op) c.ev_op->push_back(cur_op);
     hipEvent_t a, b;
     HIPCHK(hipEventCreate(&a));
-    HIPCHK(hipEventCreate(&b));
+    if (hipError_t e = hipEventCreate(&b); e != hipSuccess) {
+      hipEventDestroy(a);
+      return fail(ITSD_ERR_HIP, std::string("hipEventCreate(&b): ") + hipGetErrorString(e));
+    }
     HIPCHK(hipEventRecord(a, s));
     itsd::g_last_kernel = nullptr;
     int r = fn();
@@ -1256,6 +1254,108 @@ int check_batch(itsd_unet* u, int n) {
                                       std::to_string(u->d.max_batch) + "]");
   return ITSD_OK;
 }
+
+// The two pass shapes. forward: one time-embedding row an image (proj_buf, from temb_rows), the batch as given, the
+// tail writes eps to eps_out.
+RunCtx forward_ctx(const itsd_unet* u, int n, const float* x, const int32_t* labels, float* eps_out) {
+  RunCtx c{};
+  c.nb = n; c.x = x; c.x_mod = n;
+  c.temb = u->proj_buf; c.tsel = nullptr; c.temb_img_stride = u->sumC;
+  c.labels = labels; c.label_mod = n; c.uncond_from = -1;
+  c.tail.n = n; c.tail.cfg = 0; c.tail.step_mode = 0; c.tail.eps_out = eps_out;
+  return c;
+}
+
+// step: the sampler's program on the state x -- the schedule's time-embedding table, its row selected on the device
+// through d_t, the doubled cond||uncond batch and the guided tail for CFG. The caller sets tail.step_mode and that
+// mode's operands.
+RunCtx step_ctx(const itsd_unet* u, int n, float* x, const int32_t* labels) {
+  RunCtx c{};
+  c.nb = u->cfg ? 2 * n : n;
+  c.x = x; c.x_mod = n;
+  c.temb = u->temb_table; c.tsel = u->d_t; c.temb_img_stride = 0;
+  c.labels = labels; c.label_mod = n; c.uncond_from = u->cfg ? n : -1;
+  c.tail.n = n; c.tail.cfg = u->cfg ? 1 : 0; c.tail.guide_w = u->guide_w; c.tail.guide_w1 = u->guide_w1;
+  c.tail.x = x;
+  return c;
+}
+
+// The stream hand-over of an entry point that works on u->stream for a caller on another stream. enter: the handle's
+// device is made current and u->stream waits for what the caller's stream (cs) has queued; leave (the success path
+// only): the caller's stream waits for what u->stream has queued.
+int enter_stream(itsd_unet* u, hipStream_t cs) {
+  HIPCHK(hipSetDevice(u->device));
+  HIPCHK(hipEventRecord(u->ev_in, cs));
+  HIPCHK(hipStreamWaitEvent(u->stream, u->ev_in, 0));
+  return ITSD_OK;
+}
+int leave_stream(itsd_unet* u, hipStream_t cs) {
+  HIPCHK(hipEventRecord(u->ev_out, u->stream));
+  HIPCHK(hipStreamWaitEvent(cs, u->ev_out, 0));
+  return ITSD_OK;
+}
+
+// The step graph of (n, labels present, noise pointer, option generation): the cached one, or one step of c (the
+// program, then the step counter's decrement) captured on u->stream, instantiated and cached -- 4 entries, the oldest
+// out. A failed capture is ended and its graph destroyed before the error is returned.
+int step_graph(itsd_unet* u, const RunCtx& c, int n, bool labels, const float* noise, hipGraphExec_t* exec) {
+  const auto key = std::make_tuple(n, labels, noise, itsd::g_option_gen);
+  for (auto& g : u->graphs)
+    if (g.key == key) { *exec = g.exec; return ITSD_OK; }
+  hipStream_t s = u->stream;
+  HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+  int r = run_program(u, c, resolve_program(u, c), s);
+  if (r == ITSD_OK && launch_add_int(u->d_t, -1, s) != hipSuccess) r = fail(ITSD_ERR_HIP, "add_int");
+  hipGraph_t graph = nullptr;
+  hipError_t e = hipStreamEndCapture(s, &graph);
+  if (r != ITSD_OK) { if (graph) hipGraphDestroy(graph); return r; }
+  if (e != hipSuccess) return fail(ITSD_ERR_HIP, std::string("capture: ") + hipGetErrorString(e));
+  e = hipGraphInstantiate(exec, graph, nullptr, nullptr, 0);
+  hipGraphDestroy(graph);
+  if (e != hipSuccess) return fail(ITSD_ERR_HIP, std::string("instantiate: ") + hipGetErrorString(e));
+  if (u->graphs.size() >= 4) { hipGraphExecDestroy(u->graphs.front().exec); u->graphs.erase(u->graphs.begin()); }
+  u->graphs.push_back({key, *exec});
+  ++u->graph_captures;
+  return ITSD_OK;
+}
+
+// What a profile entry point holds for one call: the eps output, CFG's all-zero labels (the unconditional row for
+// every image: the guided batch's launches, shapes and FLOPs), the event pairs and the census's per-launch records.
+// The destructor releases them on every return path, a failed run's events included.
+struct ProfileScratch {
+  float* eps = nullptr;
+  int32_t* lab0 = nullptr;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> evs;
+  std::vector<int> kinds, kid, eop;
+  std::vector<double> fl;
+  ~ProfileScratch() {
+    for (auto& p : evs) {
+      if (p.first) hipEventDestroy(p.first);
+      if (p.second) hipEventDestroy(p.second);
+    }
+    hipFree(eps);
+    hipFree(lab0);
+  }
+  // What the three entry points open with: the caller's stream (cs) drained, the buffers, one time-embedding row an
+  // image in proj_buf.
+  int begin(itsd_unet* u, const int32_t* t, int n, hipStream_t cs) {
+    CHK(check_batch(u, n));
+    HIPCHK(hipSetDevice(u->device));
+    u->last_forward_n = 0;  // (the tail input is overwritten: itsd_unet_representation refuses until the next forward)
+    HIPCHK(hipStreamSynchronize(cs));
+    HIPCHK(hipMalloc(&eps, (size_t)n * 3 * u->H * u->H * 4));
+    if (u->cfg) {
+      HIPCHK(hipMalloc(&lab0, (size_t)n * 4));
+      HIPCHK(hipMemsetAsync(lab0, 0, (size_t)n * 4, u->stream));
+    }
+    return temb_rows(u, t, n, 0, false, u->proj_buf, u->stream);
+  }
+  // c records its launches here (ids: also each launch's kernel id and program op)
+  void census(RunCtx& c, bool ids) {
+    c.census = true; c.evs = &evs; c.ev_kind = &kinds; c.ev_flops = &fl;
+    if (ids) { c.ev_kid = &kid; c.ev_op = &eop; }
+  }
+};
 
 }  // namespace
 
@@ -1501,20 +1601,13 @@ int itsd_unet_forward(itsd_unet* u, const float* x, const int32_t* t, const int3
   CHK(check_batch(u, n));
   hipStream_t cs = (hipStream_t)stream;
   hipStream_t s = u->stream;
-  HIPCHK(hipEventRecord(u->ev_in, cs));
-  HIPCHK(hipStreamWaitEvent(s, u->ev_in, 0));
+  CHK(enter_stream(u, cs));
   CHK(temb_rows(u, t, n, 0, false, u->proj_buf, s));
-  RunCtx c{};
-  c.nb = n; c.x = x; c.x_mod = n;
-  c.temb = u->proj_buf; c.tsel = nullptr; c.temb_img_stride = u->sumC;
-  c.labels = labels; c.label_mod = n; c.uncond_from = -1;
-  c.tail.n = n; c.tail.cfg = 0; c.tail.step_mode = 0; c.tail.eps_out = eps;
+  const RunCtx c = forward_ctx(u, n, x, labels, eps);
   HIPCHK(hipMemsetAsync(u->d_nan + 1, 0, 4, s));  // this forward's hand-off status (itsd_unet_query "status")
   CHK(run_program(u, c, resolve_program(u, c), s));
   u->last_forward_n = n;
-  HIPCHK(hipEventRecord(u->ev_out, s));
-  HIPCHK(hipStreamWaitEvent(cs, u->ev_out, 0));
-  return ITSD_OK;
+  return leave_stream(u, cs);
 }
 
 int itsd_unet_representation(itsd_unet* u, float* repr, int n, void* stream) {
@@ -1522,17 +1615,13 @@ int itsd_unet_representation(itsd_unet* u, float* repr, int n, void* stream) {
   if (u->last_forward_n == 0) return fail(ITSD_ERR_INVALID, "itsd_unet_representation: no itsd_unet_forward on this handle yet");
   if (n < 1 || n > u->last_forward_n)
     return fail(ITSD_ERR_INVALID, "itsd_unet_representation: n outside [1, last forward's batch]");
-  HIPCHK(hipSetDevice(u->device));
   const Act& A = u->acts[u->tail_in];
   hipStream_t cs = (hipStream_t)stream;
   hipStream_t s = u->stream;
-  HIPCHK(hipEventRecord(u->ev_in, cs));
-  HIPCHK(hipStreamWaitEvent(s, u->ev_in, 0));
+  CHK(enter_stream(u, cs));
   HIPCHK(u->bf16 ? launch_nhwc_to_nchw<bf16_t>(u->ap(u->tail_in), repr, n, A.H * A.W, A.C, s)
                  : launch_nhwc_to_nchw<float>(u->ap(u->tail_in), repr, n, A.H * A.W, A.C, s));
-  HIPCHK(hipEventRecord(u->ev_out, s));
-  HIPCHK(hipStreamWaitEvent(cs, u->ev_out, 0));
-  return ITSD_OK;
+  return leave_stream(u, cs);
 }
 
 int itsd_set_schedule(itsd_unet* u, int T, const float* coeff1, const float* coeff2, const float* sqrt_var, float w) {
@@ -1566,27 +1655,18 @@ int itsd_sampler_run(itsd_unet* u, float* x, const int32_t* labels, int n, int t
   if (u->cfg && !labels) return fail(ITSD_ERR_INVALID, "CFG sampler needs labels");
   CHK(check_batch(u, n));
   if (t_begin >= u->T_sched || t_end < 0 || t_end > t_begin) return fail(ITSD_ERR_INVALID, "bad step range");
-  HIPCHK(hipSetDevice(u->device));
-  u->last_forward_n = 0;  // (the tail input is overwritten: itsd_unet_representation refuses until the next forward)
   hipStream_t cs = (hipStream_t)stream;
   hipStream_t s = u->stream;
-  HIPCHK(hipEventRecord(u->ev_in, cs));
-  HIPCHK(hipStreamWaitEvent(s, u->ev_in, 0));
+  CHK(enter_stream(u, cs));
+  u->last_forward_n = 0;  // (the tail input is overwritten: itsd_unet_representation refuses until the next forward)
   const int clip_at = (flags & ITSD_RUN_CLIP) ? t_end : -1;
   const size_t xbytes = (size_t)n * 3 * u->H * u->H * 4;
   HIPCHK(hipMemcpyAsync(u->x_state, x, xbytes, hipMemcpyDeviceToDevice, s));
   if (labels) HIPCHK(hipMemcpyAsync(u->lab_state, labels, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
-  float* xs = u->x_state;
-  const int32_t* ls = labels ? u->lab_state : nullptr;
 
-  RunCtx c{};
-  c.nb = u->cfg ? 2 * n : n;
-  c.x = xs; c.x_mod = n;
-  c.temb = u->temb_table; c.tsel = u->d_t; c.temb_img_stride = 0;
-  c.labels = ls; c.label_mod = n; c.uncond_from = u->cfg ? n : -1;
+  RunCtx c = step_ctx(u, n, u->x_state, labels ? u->lab_state : nullptr);
   TailArgs& t = c.tail;
-  t.n = n; t.cfg = u->cfg ? 1 : 0; t.guide_w = u->guide_w; t.guide_w1 = u->guide_w1;
-  t.step_mode = 1; t.x = xs; t.tsel = u->d_t;
+  t.step_mode = 1; t.tsel = u->d_t;
   t.coeff1 = u->coeff1; t.coeff2 = u->coeff2; t.sqrt_var = u->sqrt_var;
   t.noise = noise; t.run = u->d_run; t.nan_flag = u->d_nan;
 
@@ -1595,25 +1675,8 @@ int itsd_sampler_run(itsd_unet* u, float* x, const int32_t* labels, int n, int t
   HIPCHK(launch_run_begin(u->d_t, t_begin, u->d_nan, u->d_run, rp, s));
   const int steps = t_begin - t_end + 1;
   if (flags & ITSD_RUN_GRAPH) {
-    auto key = std::make_tuple(n, labels != nullptr, noise, itsd::g_option_gen);
     hipGraphExec_t exec = nullptr;
-    for (auto& g : u->graphs)
-      if (g.key == key) exec = g.exec;
-    if (!exec) {
-      HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-      int r = run_program(u, c, resolve_program(u, c), s);
-      if (r == ITSD_OK && launch_add_int(u->d_t, -1, s) != hipSuccess) r = fail(ITSD_ERR_HIP, "add_int");
-      hipGraph_t graph = nullptr;
-      hipError_t e = hipStreamEndCapture(s, &graph);
-      if (r != ITSD_OK) { if (graph) hipGraphDestroy(graph); return r; }
-      if (e != hipSuccess) return fail(ITSD_ERR_HIP, std::string("capture: ") + hipGetErrorString(e));
-      e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-      hipGraphDestroy(graph);
-      if (e != hipSuccess) return fail(ITSD_ERR_HIP, std::string("instantiate: ") + hipGetErrorString(e));
-      if (u->graphs.size() >= 4) { hipGraphExecDestroy(u->graphs.front().exec); u->graphs.erase(u->graphs.begin()); }
-      u->graphs.push_back({key, exec});
-      ++u->graph_captures;
-    }
+    CHK(step_graph(u, c, n, labels != nullptr, noise, &exec));
     for (int i = 0; i < steps; ++i) HIPCHK(hipGraphLaunch(exec, s));
   } else {
     const std::vector<ConvLaunch> convs = resolve_program(u, c);  // (the steps differ in device state only)
@@ -1623,8 +1686,7 @@ int itsd_sampler_run(itsd_unet* u, float* x, const int32_t* labels, int n, int t
     }
   }
   HIPCHK(hipMemcpyAsync(x, u->x_state, xbytes, hipMemcpyDeviceToDevice, s));
-  HIPCHK(hipEventRecord(u->ev_out, s));
-  HIPCHK(hipStreamWaitEvent(cs, u->ev_out, 0));
+  CHK(leave_stream(u, cs));
   if (flags & ITSD_RUN_SYNC) {
     HIPCHK(hipStreamSynchronize(s));
     int flag[2] = {0, 0};
@@ -1647,26 +1709,16 @@ int itsd_sampler_predict_x0(itsd_unet* u, const float* x, const int32_t* labels,
   CHK(check_batch(u, n));
   if (t < 0 || t >= u->T_sched)
     return fail(ITSD_ERR_INVALID, "step " + std::to_string(t) + " outside [0, T_sched=" + std::to_string(u->T_sched) + ")");
-  HIPCHK(hipSetDevice(u->device));
-  u->last_forward_n = 0;  // (the tail input is overwritten: itsd_unet_representation refuses until the next forward)
   hipStream_t cs = (hipStream_t)stream;
   hipStream_t s = u->stream;
-  HIPCHK(hipEventRecord(u->ev_in, cs));
-  HIPCHK(hipStreamWaitEvent(s, u->ev_in, 0));
-  RunCtx c{};
-  c.nb = u->cfg ? 2 * n : n;
-  c.x = x; c.x_mod = n;
-  c.temb = u->temb_table; c.tsel = u->d_t; c.temb_img_stride = 0;
-  c.labels = labels; c.label_mod = n; c.uncond_from = u->cfg ? n : -1;
-  TailArgs& ta = c.tail;
-  ta.n = n; ta.cfg = u->cfg ? 1 : 0; ta.guide_w = u->guide_w; ta.guide_w1 = u->guide_w1;
-  ta.step_mode = 2; ta.x = const_cast<float*>(x); ta.a0 = a0; ta.b0 = b0; ta.x0_out = x0;
+  CHK(enter_stream(u, cs));
+  u->last_forward_n = 0;  // (the tail input is overwritten: itsd_unet_representation refuses until the next forward)
+  RunCtx c = step_ctx(u, n, const_cast<float*>(x), labels);
+  c.tail.step_mode = 2; c.tail.a0 = a0; c.tail.b0 = b0; c.tail.x0_out = x0;
   HIPCHK(launch_set_int(u->d_t, t, s));
   HIPCHK(hipMemsetAsync(u->d_nan + 1, 0, 4, s));  // this forward's hand-off status (itsd_unet_query "status")
   CHK(run_program(u, c, resolve_program(u, c), s));
-  HIPCHK(hipEventRecord(u->ev_out, s));
-  HIPCHK(hipStreamWaitEvent(cs, u->ev_out, 0));
-  return ITSD_OK;
+  return leave_stream(u, cs);
 }
 
 int itsd_branch(float* dst, const float* src, const int32_t* parents, int n_src, int n_dst, int64_t per_cand, float a,
@@ -1739,41 +1791,26 @@ int itsd_profile_forward(itsd_unet* u, const float* x, const int32_t* t, int n, 
                          int* conv_launches, double* total_ms, void* stream) {
   if (!u || !x || !t) return fail(ITSD_ERR_INVALID, "null argument");
   if (u->cfg) return fail(ITSD_ERR_INVALID, "profile_forward: DDPM only");
-  CHK(check_batch(u, n));
-  HIPCHK(hipSetDevice(u->device));
-  u->last_forward_n = 0;  // (the tail input is overwritten: itsd_unet_representation refuses until the next forward)
   hipStream_t s = u->stream;
-  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-  float* eps = nullptr;
-  HIPCHK(hipMalloc(&eps, (size_t)n * 3 * u->H * u->H * 4));
-  CHK(temb_rows(u, t, n, 0, false, u->proj_buf, s));
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> evs;
-  std::vector<int> kinds;
-  std::vector<double> fl;
-  RunCtx c{};
-  c.nb = n; c.x = x; c.x_mod = n;
-  c.temb = u->proj_buf; c.temb_img_stride = u->sumC;
-  c.label_mod = n; c.uncond_from = -1;
-  c.tail.n = n; c.tail.step_mode = 0; c.tail.eps_out = eps;
-  c.census = true; c.evs = &evs; c.ev_kind = &kinds; c.ev_flops = &fl;
+  ProfileScratch p;
+  CHK(p.begin(u, t, n, (hipStream_t)stream));
+  RunCtx c = forward_ctx(u, n, x, nullptr, p.eps);
+  p.census(c, false);
   int r = run_program(u, c, resolve_program(u, c), s);
   hipError_t e = hipStreamSynchronize(s);
-  double cm = 0, cf = 0, tm = 0;
-  int cl = 0;
-  for (size_t i = 0; i < evs.size(); ++i) {
-    float ms = 0.f;
-    if (r == ITSD_OK && e == hipSuccess) hipEventElapsedTime(&ms, evs[i].first, evs[i].second);
-    tm += ms;
-    if (kinds[i] == OP_CONV || kinds[i] == kCensusConvGN || kinds[i] == kCensusConvGNW ||
-        kinds[i] == kCensusConvGNW4) {
-      cm += ms; cf += fl[i]; ++cl;
-    }
-    hipEventDestroy(evs[i].first);
-    hipEventDestroy(evs[i].second);
-  }
-  hipFree(eps);
   CHK(r);
   HIPCHK(e);
+  double cm = 0, cf = 0, tm = 0;
+  int cl = 0;
+  for (size_t i = 0; i < p.evs.size(); ++i) {
+    float ms = 0.f;
+    hipEventElapsedTime(&ms, p.evs[i].first, p.evs[i].second);
+    tm += ms;
+    if (p.kinds[i] == OP_CONV || p.kinds[i] == kCensusConvGN || p.kinds[i] == kCensusConvGNW ||
+        p.kinds[i] == kCensusConvGNW4) {
+      cm += ms; cf += p.fl[i]; ++cl;
+    }
+  }
   if (conv_ms) *conv_ms = cm;
   if (conv_flops) *conv_flops = cf;
   if (conv_launches) *conv_launches = cl;
@@ -1785,46 +1822,25 @@ int itsd_profile_op(itsd_unet* u, const float* x, const int32_t* t, int n, int o
                     void* stream) {
   if (!u || !x || !t || !ms || reps < 1) return fail(ITSD_ERR_INVALID, "null argument or reps < 1");
   if (op_index < 1 || op_index > (int)u->ops.size()) return fail(ITSD_ERR_INVALID, "profile_op: op_index out of range");
-  CHK(check_batch(u, n));
-  HIPCHK(hipSetDevice(u->device));
-  u->last_forward_n = 0;  // (the tail input is overwritten: itsd_unet_representation refuses until the next forward)
   hipStream_t s = u->stream;
-  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-  float* eps = nullptr;
-  HIPCHK(hipMalloc(&eps, (size_t)n * 3 * u->H * u->H * 4));
-  // CFG: label 0 (the unconditional row) for every image -- the guided batch's launches, shapes
-  // and FLOPs
-  int32_t* lab0 = nullptr;
-  if (u->cfg) {
-    HIPCHK(hipMalloc(&lab0, (size_t)n * 4));
-    HIPCHK(hipMemsetAsync(lab0, 0, (size_t)n * 4, s));
-  }
-  int r = temb_rows(u, t, n, 0, false, u->proj_buf, s);
-  RunCtx c{};
-  c.nb = n; c.x = x; c.x_mod = n;
-  c.temb = u->proj_buf; c.temb_img_stride = u->sumC;
-  c.labels = lab0; c.label_mod = n; c.uncond_from = -1;
-  c.tail.n = n; c.tail.step_mode = 0; c.tail.eps_out = eps;
+  ProfileScratch p;
+  CHK(p.begin(u, t, n, (hipStream_t)stream));
+  const RunCtx c = forward_ctx(u, n, x, p.lab0, p.eps);
   const std::vector<ConvLaunch> convs = resolve_program(u, c);
-  if (r == ITSD_OK) r = run_program(u, c, convs, s);  // every op's inputs in place
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  hipError_t e = hipEventCreate(&e0);
-  if (e == hipSuccess) e = hipEventCreate(&e1);
+  CHK(run_program(u, c, convs, s));  // every op's inputs in place
+  p.evs.push_back({nullptr, nullptr});
+  hipEvent_t &e0 = p.evs[0].first, &e1 = p.evs[0].second;
+  HIPCHK(hipEventCreate(&e0));
+  HIPCHK(hipEventCreate(&e1));
   const Op& o = u->ops[op_index - 1];
   const ConvLaunch* cl = &convs[op_index - 1];
-  if (r == ITSD_OK && e == hipSuccess) r = launch_op(u, o, c, cl, s);  // warm
-  if (r == ITSD_OK && e == hipSuccess) e = hipEventRecord(e0, s);
-  for (int i = 0; i < reps && r == ITSD_OK && e == hipSuccess; ++i) r = launch_op(u, o, c, cl, s);
-  if (r == ITSD_OK && e == hipSuccess) e = hipEventRecord(e1, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  CHK(launch_op(u, o, c, cl, s));  // warm
+  HIPCHK(hipEventRecord(e0, s));
+  for (int i = 0; i < reps; ++i) CHK(launch_op(u, o, c, cl, s));
+  HIPCHK(hipEventRecord(e1, s));
+  HIPCHK(hipStreamSynchronize(s));
   float m = 0.f;
-  if (r == ITSD_OK && e == hipSuccess) e = hipEventElapsedTime(&m, e0, e1);
-  if (e0) hipEventDestroy(e0);
-  if (e1) hipEventDestroy(e1);
-  hipFree(eps);
-  if (lab0) hipFree(lab0);
-  CHK(r);
-  HIPCHK(e);
+  HIPCHK(hipEventElapsedTime(&m, e0, e1));
   *ms = (double)m / reps;
   return ITSD_OK;
 }
@@ -1832,48 +1848,31 @@ int itsd_profile_op(itsd_unet* u, const float* x, const int32_t* t, int n, int o
 int itsd_profile_ops(itsd_unet* u, const float* x, const int32_t* t, int n, int max_ops, int* kinds, double* ms,
                      double* flops, int* shapes, int* n_ops, void* stream) {
   if (!u || !x || !t || !n_ops) return fail(ITSD_ERR_INVALID, "null argument");
-  CHK(check_batch(u, n));
-  HIPCHK(hipSetDevice(u->device));
-  u->last_forward_n = 0;  // (the tail input is overwritten: itsd_unet_representation refuses until the next forward)
   hipStream_t s = u->stream;
-  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-  float* eps = nullptr;
-  HIPCHK(hipMalloc(&eps, (size_t)n * 3 * u->H * u->H * 4));
-  int32_t* lab0 = nullptr;  // CFG: label 0 for every image (as itsd_profile_op)
-  if (u->cfg) {
-    HIPCHK(hipMalloc(&lab0, (size_t)n * 4));
-    HIPCHK(hipMemsetAsync(lab0, 0, (size_t)n * 4, s));
-  }
-  CHK(temb_rows(u, t, n, 0, false, u->proj_buf, s));
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> evs;
-  std::vector<int> kd, kid, eop;
-  std::vector<double> fl;
-  RunCtx c{};
-  c.nb = n; c.x = x; c.x_mod = n;
-  c.temb = u->proj_buf; c.temb_img_stride = u->sumC;
-  c.labels = lab0; c.label_mod = n; c.uncond_from = -1;
-  c.tail.n = n; c.tail.step_mode = 0; c.tail.eps_out = eps;
-  c.census = true; c.evs = &evs; c.ev_kind = &kd; c.ev_flops = &fl; c.ev_kid = &kid; c.ev_op = &eop;
+  ProfileScratch p;
+  CHK(p.begin(u, t, n, (hipStream_t)stream));
+  RunCtx c = forward_ctx(u, n, x, p.lab0, p.eps);
+  p.census(c, true);
   const std::vector<ConvLaunch> convs = resolve_program(u, c);
   int r = run_program(u, c, convs, s);
   hipError_t e = hipStreamSynchronize(s);
+  CHK(r);
+  HIPCHK(e);
   // launch order: head, ops..., tail GN, tail
   int k = 0;
-  for (size_t i = 0; i < evs.size(); ++i) {
+  for (size_t i = 0; i < p.evs.size() && k < max_ops; ++i, ++k) {
+    const int op = p.eop[i];
     float m = 0.f;
-    if (r == ITSD_OK && e == hipSuccess) hipEventElapsedTime(&m, evs[i].first, evs[i].second);
-    hipEventDestroy(evs[i].first);
-    hipEventDestroy(evs[i].second);
-    if (k >= max_ops) continue;
-    if (kinds) kinds[k] = (kid[i] << 8) | (kd[i] & 0xff);
+    hipEventElapsedTime(&m, p.evs[i].first, p.evs[i].second);
+    if (kinds) kinds[k] = (p.kid[i] << 8) | (p.kinds[i] & 0xff);
     if (ms) ms[k] = m;
-    if (flops) flops[k] = fl[i];
+    if (flops) flops[k] = p.fl[i];
     if (shapes) {
       int* sh = shapes + 8 * k;
       for (int q = 0; q < 8; ++q) sh[q] = 0;
-      sh[6] = eop[i];
-      if (eop[i] >= 1) {
-        const Op& o = u->ops[eop[i] - 1];
+      sh[6] = op;
+      if (op >= 1) {
+        const Op& o = u->ops[op - 1];
         const Act& out = u->acts[o.dst >= 0 ? o.dst : o.src1];
         const Act& in = u->acts[o.src1];
         sh[0] = n * out.H * out.W;
@@ -1887,17 +1886,12 @@ int itsd_profile_ops(itsd_unet* u, const float* x, const int32_t* t, int n, int 
         sh[7] = (o.resid >= 0 ? 1 : 0) | (out.stats != SIZE_MAX ? 2 : 0) | (o.coef != SIZE_MAX ? 4 : 0);
         // a block2 conv with its 1x1 shortcut folded in as K slices: no residual operand; the shortcut's input
         // channels in bits 8..
-        const ConvLaunch& cl = convs[eop[i] - 1];
+        const ConvLaunch& cl = convs[op - 1];
         if (cl.p.sc_split) sh[7] = (sh[7] & ~1) | ((cl.a.sc_C1 + cl.a.sc_C2) << 8);
       }
     }
-    ++k;
   }
   *n_ops = k;
-  hipFree(eps);
-  if (lab0) hipFree(lab0);
-  CHK(r);
-  HIPCHK(e);
   return ITSD_OK;
 }
 

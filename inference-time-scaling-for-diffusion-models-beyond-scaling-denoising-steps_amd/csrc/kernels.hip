@@ -1610,19 +1610,94 @@ __device__ __forceinline__ float philox_normal(unsigned long long seed, unsigned
 
 // ============================================================================ tail conv + sampler step
 // tail = GN -> Swish -> Conv2d(C, 3, 3, padding=1) (Model.py:252-256, 282). The GN+Swish
-// output g is produced by groupnorm_kernel; this kernel does the 3-output conv per
-// pixel with the weights in LDS and then either writes eps (forward API) or applies
-// the ancestral update of Diffusion.py:67-71,96-100 in place on x:
-//   mean = coeff1[t]*x - coeff2[t]*eps ;  x = mean + sqrt(var[t]) * z  (z = 0 at t = 0)
+// output g is produced by groupnorm_kernel (tail_mfma_kernel applies it itself); the three kernels below do the
+// 3-output conv per pixel and hand each output element's eps to tail_finish, which ends in one of three ways:
+//   eps  (TailArgs::step_mode 0, the forward API)  eps_out = eps
+//   step (step_mode 1)  the ancestral update of Diffusion.py:67-71,96-100 in place on x:
+//          mean = coeff1[t]*x - coeff2[t]*eps ;  x = mean + sqrt(var[t]) * z  (z = 0 at t = 0; injected or Philox),
+//          clipped to [-1, 1] at step RunParams::clip_at; a NaN (tested before the clip) is reported to the caller,
+//          which raises nan_flag
+//   x0   (step_mode 2, its own instantiation: the eps / step kernels' code is what it was)
+//          x0_out = clip(a0 * x - b0 * eps, -1, 1)   (the x_0 estimate of the state x at this step)
+//          x is only read, no noise is drawn, the NaN flag is not touched, a.run and the schedule tables are not read.
 // CFG: eps = (1+w) eps_c - w eps_u (DiffusionCondition.py:85) with the unconditional
-// branch at image index img + n of g.
-// X0 (TailArgs::step_mode 2, its own instantiation: the eps / step kernels' code is what it was): the epilogue writes
-//   x0 = clip(a0 * x - b0 * eps, -1, 1)   (the x_0 estimate of the state x at this step, guided eps for CFG)
-// to x0_out; x is only read, no noise is drawn, the NaN flag is not touched, a.run and the schedule tables are not read.
+// branch at image index img + n of g (guided before tail_finish, in all three modes).
 __device__ __forceinline__ float tail_x0(float a0, float b0, float xv, float e) {
 #pragma clang fp contract(off)
   const float v = a0 * xv - b0 * e;
   return fminf(fmaxf(v, -1.0f), 1.0f);
+}
+
+// The step's scalars: row t of the schedule tables and the run's parameters. Loaded in step mode only; the other two
+// modes read none of them.
+struct TailStep {
+  int t = 0;
+  float c1 = 0.f, c2 = 0.f, sv = 0.f;
+  unsigned long long seed = 0;
+  long long noise_offset = 0;
+  int clip_at = -1;
+};
+template <bool X0>
+__device__ __forceinline__ TailStep tail_step_load(const TailArgs& a) {
+  TailStep s;
+  if (!X0 && a.step_mode) {
+    s.t = *a.tsel;
+    s.seed = a.run->seed;
+    s.noise_offset = a.run->noise_offset;
+    s.clip_at = a.run->clip_at;
+    s.c1 = a.coeff1[s.t];
+    s.c2 = a.coeff2[s.t];
+    s.sv = a.sqrt_var[s.t];
+  }
+  return s;
+}
+
+// x at NCHW offset o where the epilogue reads it (the eps mode has no x)
+template <bool X0>
+__device__ __forceinline__ float tail_x(const TailArgs& a, size_t o) {
+  return (X0 || a.step_mode) ? a.x[o] : 0.f;
+}
+
+// NCHW offset of output channel oc at pixel opx of a block of full rows that starts at row y0 of image img
+__device__ __forceinline__ size_t tail_offset(int img, int y0, int opx, int oc, int H, int W) {
+  const int rem = (y0 + opx / W) * W + (opx - (opx / W) * W);
+  return ((size_t)img * 3 + oc) * (H * W) + rem;
+}
+
+// One output element: its (guided) eps e, its NCHW offset o, its x value xv (tail_x) and the step's scalars. Returns
+// whether the step's new x is NaN (false in the other two modes).
+template <bool X0>
+__device__ __forceinline__ bool tail_finish(const TailArgs& a, const TailStep& s, size_t o, float xv, float e) {
+#pragma clang fp contract(off)
+  if constexpr (X0) {
+    a.x0_out[o] = tail_x0(a.a0, a.b0, xv, e);
+    return false;
+  }
+  if (!a.step_mode) {
+    a.eps_out[o] = e;
+    return false;
+  }
+  const float mean = s.c1 * xv - s.c2 * e;
+  float xn = mean;
+  if (s.t > 0) {
+    const float z = a.noise ? a.noise[(size_t)s.t * a.n * 3 * (a.H * a.W) + o]
+                            : philox_normal(s.seed, (unsigned)s.t, (unsigned long long)(s.noise_offset + (long long)o));
+    xn = mean + s.sv * z;
+  }
+  const bool bad = xn != xn;
+  if (s.t == s.clip_at) xn = fminf(fmaxf(xn, -1.0f), 1.0f);
+  a.x[o] = xn;
+  return bad;
+}
+
+// reference layout w[co][ci][ky][kx] -> wl[(tap*C + ci)*3 + co] (256 threads)
+__device__ __forceinline__ void tail_stage_weights(float* wl, const float* w, int C) {
+  for (int i = threadIdx.x; i < 27 * C; i += 256) {
+    const int co = i / (C * 9);
+    const int r = i - co * C * 9;
+    const int ci = r / 9, tap = r - ci * 9;
+    wl[(tap * C + ci) * 3 + co] = w[i];
+  }
 }
 
 template <typename T, bool X0 = false>
@@ -1630,13 +1705,7 @@ __global__ __launch_bounds__(256) void tail_kernel(TailArgs a) {
   constexpr int EPC = 16 / (int)sizeof(T);
   extern __shared__ __attribute__((aligned(16))) float wl[];  // [9][C][3]
   const int C = a.C;
-  for (int i = threadIdx.x; i < 27 * C; i += 256) {
-    // reference layout w[co][ci][ky][kx] -> wl[(tap*C + ci)*3 + co]
-    const int co = i / (C * 9);
-    const int r = i - co * C * 9;
-    const int ci = r / 9, tap = r - ci * 9;
-    wl[(tap * C + ci) * 3 + co] = a.w[i];
-  }
+  tail_stage_weights(wl, a.w, C);
   __syncthreads();
   const int HW = a.H * a.W;
   const long long pix = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -1680,40 +1749,14 @@ __global__ __launch_bounds__(256) void tail_kernel(TailArgs a) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) eps[c] = w1 * eps[c] - a.guide_w * u[c];
   }
-  if constexpr (X0) {
+  const TailStep st = tail_step_load<X0>(a);
+  bool bad = false;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const size_t o = ((size_t)img * 3 + c) * HW + rem;
-      a.x0_out[o] = tail_x0(a.a0, a.b0, a.x[o], eps[c]);
-    }
-    return;
+  for (int c = 0; c < 3; ++c) {
+    const size_t o = ((size_t)img * 3 + c) * HW + rem;
+    bad |= tail_finish<X0>(a, st, o, tail_x<X0>(a, o), eps[c]);
   }
-  if (!a.step_mode) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) a.eps_out[((size_t)img * 3 + c) * HW + rem] = eps[c];
-    return;
-  }
-  {
-#pragma clang fp contract(off)
-    const int t = *a.tsel;
-    const float c1 = a.coeff1[t], c2 = a.coeff2[t], sv = a.sqrt_var[t];
-    bool bad = false;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const size_t o = ((size_t)img * 3 + c) * HW + rem;
-      const float xv = a.x[o];
-      const float mean = c1 * xv - c2 * eps[c];
-      float xn = mean;
-      if (t > 0) {
-        const float z = a.noise ? a.noise[(size_t)t * a.n * 3 * HW + o] : philox_normal(a.run->seed, (unsigned)t, (unsigned long long)(a.run->noise_offset + (long long)o));
-        xn = mean + sv * z;
-      }
-      bad |= (xn != xn);
-      if (t == a.run->clip_at) xn = fminf(fmaxf(xn, -1.0f), 1.0f);
-      a.x[o] = xn;
-    }
-    if (bad) atomicOr(a.nan_flag, 1);
-  }
+  if (bad) atomicOr(a.nan_flag, 1);
 }
 
 // Tiled tail: one block per 64 output pixels (64/W full rows of one image); the input
@@ -1729,12 +1772,7 @@ __global__ __launch_bounds__(256) void tail2_kernel(TailArgs a) {
   const int PST = C * (int)sizeof(T) + 16;
   float* wl = (float*)tsm;           // [9][C][3]
   char* halo = tsm + 27 * C * 4;     // [(rpb+2)*(W+2)] pixels of PST bytes
-  for (int i = threadIdx.x; i < 27 * C; i += 256) {
-    const int co = i / (C * 9);
-    const int r = i - co * C * 9;
-    const int ci = r / 9, tap = r - ci * 9;
-    wl[(tap * C + ci) * 3 + co] = a.w[i];
-  }
+  tail_stage_weights(wl, a.w, C);
   const int bpi = H / rpb;
   const int img = blockIdx.x / bpi, y0 = (blockIdx.x % bpi) * rpb;
   // wave = channel quarter (its weight reads are wave-uniform LDS broadcasts),
@@ -1798,31 +1836,8 @@ __global__ __launch_bounds__(256) void tail2_kernel(TailArgs a) {
     const float u = a.b[oc] + s;
     e = a.guide_w1 * e - a.guide_w * u;
   }
-  const int rem = (y0 + opx / W) * W + (opx - (opx / W) * W);
-  const size_t o = ((size_t)img * 3 + oc) * HW + rem;
-  if constexpr (X0) {
-    a.x0_out[o] = tail_x0(a.a0, a.b0, a.x[o], e);
-    return;
-  }
-  if (!a.step_mode) {
-    a.eps_out[o] = e;
-    return;
-  }
-  {
-#pragma clang fp contract(off)
-    const int t = *a.tsel;
-    const float xv = a.x[o];
-    const float mean = a.coeff1[t] * xv - a.coeff2[t] * e;
-    float xn = mean;
-    if (t > 0) {
-      const float z = a.noise ? a.noise[(size_t)t * a.n * 3 * HW + o]
-                              : philox_normal(a.run->seed, (unsigned)t, (unsigned long long)(a.run->noise_offset + (long long)o));
-      xn = mean + a.sqrt_var[t] * z;
-    }
-    if (xn != xn) atomicOr(a.nan_flag, 1);
-    if (t == a.run->clip_at) xn = fminf(fmaxf(xn, -1.0f), 1.0f);
-    a.x[o] = xn;
-  }
+  const size_t o = tail_offset(img, y0, opx, oc, H, W);
+  if (tail_finish<X0>(a, tail_step_load<X0>(a), o, tail_x<X0>(a, o), e)) atomicOr(a.nan_flag, 1);
 }
 
 // bf16 tail on MFMA with the tail GroupNorm+SiLU fused (Model.py:252-256 / 282, then the
@@ -1870,32 +1885,14 @@ __global__ __launch_bounds__(NTH, 2) void tail_mfma_kernel(TailArgs a) {
   // the sampler step's operands of this thread's output items (it = tid, tid + NTH, ..), loaded now: their
   // latency hides behind the halo staging and the MFMAs
   constexpr int TIT = (TM_PX * 3 + NTH - 1) / NTH;
-  float xpre[TIT];
-  int tpre = 0;
-  float c1pre = 0.f, c2pre = 0.f, svpre = 0.f;
-  unsigned long long seedpre = 0;
-  long long noffpre = 0;
-  int clippre = -1;
-  if constexpr (X0) {  // x only: the x0 epilogue reads neither a.run nor the schedule tables
+  float xpre[TIT] = {};
+  TailStep st;
+  if (X0 || a.step_mode) {
+    st = tail_step_load<X0>(a);
 #pragma unroll
     for (int k = 0; k < TIT; ++k) {
       const int it = tid + NTH * k, opx = it < TM_PX * 3 ? it / 3 : 0, oc = it < TM_PX * 3 ? it - opx * 3 : 0;
-      const int rem = (y0 + opx / W) * W + (opx - (opx / W) * W);
-      xpre[k] = a.x[((size_t)img * 3 + oc) * HW + rem];
-    }
-  } else if (a.step_mode) {
-    tpre = *a.tsel;
-    seedpre = a.run->seed;
-    noffpre = a.run->noise_offset;
-    clippre = a.run->clip_at;
-    c1pre = a.coeff1[tpre];
-    c2pre = a.coeff2[tpre];
-    svpre = a.sqrt_var[tpre];
-#pragma unroll
-    for (int k = 0; k < TIT; ++k) {
-      const int it = tid + NTH * k, opx = it < TM_PX * 3 ? it / 3 : 0, oc = it < TM_PX * 3 ? it - opx * 3 : 0;
-      const int rem = (y0 + opx / W) * W + (opx - (opx / W) * W);
-      xpre[k] = a.x[((size_t)img * 3 + oc) * HW + rem];
+      xpre[k] = a.x[tail_offset(img, y0, opx, oc, H, W)];
     }
   }
   constexpr int TB = 4096 / NTH;  // halo items a thread per batch (C = 128, 32 x 32: the whole halo in one batch)
@@ -1992,33 +1989,11 @@ __global__ __launch_bounds__(NTH, 2) void tail_mfma_kernel(TailArgs a) {
       const float u = red[(TM_PX + opx) * 3 + oc] + a.b[oc];
       e = a.guide_w1 * e - a.guide_w * u;
     }
-    const int rem = (y0 + opx / W) * W + (opx - (opx / W) * W);
-    const size_t o = ((size_t)img * 3 + oc) * HW + rem;
-    if constexpr (X0) {
-      a.x0_out[o] = tail_x0(a.a0, a.b0, xpre[k], e);
-      continue;
-    }
-    if (!a.step_mode) {
-      a.eps_out[o] = e;
-      continue;
-    }
-    {
-#pragma clang fp contract(off)
-      const int t = tpre;
-      const float xv = xpre[k];
-      const float mean = c1pre * xv - c2pre * e;
-      float xn = mean;
-      if (t > 0) {
-        const float z = a.noise ? a.noise[(size_t)t * a.n * 3 * HW + o]
-                                : philox_normal(seedpre, (unsigned)t, (unsigned long long)(noffpre + (long long)o));
-        xn = mean + svpre * z;
-      }
-      if (xn != xn) atomicOr(a.nan_flag, 1);
-      if (t == clippre) xn = fminf(fmaxf(xn, -1.0f), 1.0f);
-      a.x[o] = xn;
-    }
+    if (tail_finish<X0>(a, st, tail_offset(img, y0, opx, oc, H, W), xpre[k], e)) atomicOr(a.nan_flag, 1);
   }
 }
+
+constexpr size_t kTailSmemMax = 160 * 1024;  // the dynamic shared memory a tail kernel may ask for
 
 static size_t tail_mfma_smem_px(int px, int H, int W, int C) {
   return (size_t)(9 * C / 32) * 12 * 16 + (size_t)(px / W + 2) * (W + 2) * tail_pst(C) + 2 * px * 3 * 4 +
@@ -2026,7 +2001,7 @@ static size_t tail_mfma_smem_px(int px, int H, int W, int C) {
 }
 static bool tail_mfma_ok_px(int px, int H, int W, int C) {
   return W <= px && px % W == 0 && px / W <= H && H % (px / W) == 0 && C % 32 == 0 &&
-         tail_mfma_smem_px(px, H, W, C) <= 160 * 1024;
+         tail_mfma_smem_px(px, H, W, C) <= kTailSmemMax;
 }
 size_t tail_mfma_smem(int H, int W, int C) { return tail_mfma_smem_px(128, H, W, C); }
 bool tail_mfma_ok(int H, int W, int C) { return tail_mfma_ok_px(128, H, W, C); }
@@ -2034,21 +2009,30 @@ bool tail_mfma_ok(int H, int W, int C) { return tail_mfma_ok_px(128, H, W, C); }
 // step_mode 2 needs its operands (and nothing of the step's)
 static bool tail_x0_ok(const TailArgs& a) { return a.step_mode != 2 || (a.x && a.x0_out); }
 
+// The body of a tail launcher from its launch geometry on: launches the instantiation a.step_mode selects (X0K for the
+// x0 epilogue, PLAIN for eps and step; each under its own name, which the census and the profiles key on) and returns
+// the launch's status. BIG: the pair may use up to kTailSmemMax of dynamic shared memory; the attribute is set once.
+#define ITSD_RETURN_TAIL_LAUNCH(PLAIN, X0K, BIG, grid, block, sm, s, a)                                        \
+  do {                                                                                                         \
+    static bool attr = !(BIG);                                                                                 \
+    if (!attr) {                                                                                               \
+      for (const void* f : {(const void*)PLAIN, (const void*)X0K}) {                                           \
+        hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTailSmemMax);  \
+        if (e != hipSuccess) return e;                                                                         \
+      }                                                                                                        \
+      attr = true;                                                                                             \
+    }                                                                                                          \
+    if ((a).step_mode == 2) ITSD_LAUNCH(X0K, grid, block, sm, s, a);                                           \
+    else ITSD_LAUNCH(PLAIN, grid, block, sm, s, a);                                                            \
+    return hipGetLastError();                                                                                  \
+  } while (0)
+
 hipError_t launch_tail_mfma(const TailArgs& a, hipStream_t s) {
   if (!a.coef || !a.wmf || !tail_mfma_ok(a.H, a.W, a.C) || !tail_x0_ok(a)) return hipErrorInvalidValue;
-  static bool attr = false;
-  if (!attr) {
-    for (const void* f : {(const void*)tail_mfma_kernel<128, 512>, (const void*)tail_mfma_kernel<128, 512, true>}) {
-      hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) return e;
-    }
-    attr = true;
-  }
   const dim3 grid(a.n * (a.H / (128 / a.W)));
   const size_t sm = tail_mfma_smem_px(128, a.H, a.W, a.C);
-  if (a.step_mode == 2) ITSD_LAUNCH((tail_mfma_kernel<128, 512, true>), grid, dim3(512), sm, s, a);
-  else ITSD_LAUNCH((tail_mfma_kernel<128, 512>), grid, dim3(512), sm, s, a);
-  return hipGetLastError();
+  ITSD_RETURN_TAIL_LAUNCH((tail_mfma_kernel<128, 512>), (tail_mfma_kernel<128, 512, true>), true, grid, dim3(512), sm,
+                          s, a);
 }
 
 template <typename T>
@@ -2056,25 +2040,14 @@ hipError_t launch_tail(const TailArgs& a, hipStream_t s) {
   if (!tail_x0_ok(a)) return hipErrorInvalidValue;
   if (a.W <= 64 && 64 % a.W == 0 && a.H % (64 / a.W) == 0 && a.C % 32 == 0) {
     const size_t sm = 27 * a.C * 4 + (size_t)(64 / a.W + 2) * (a.W + 2) * (a.C * sizeof(T) + 16) + 2 * 4 * 64 * 3 * 4;
-    if (sm > 160 * 1024) return hipErrorInvalidValue;
-    static bool attr = false;
-    if (!attr) {
-      for (const void* f : {(const void*)tail2_kernel<T>, (const void*)tail2_kernel<T, true>}) {
-        hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-      }
-      attr = true;
-    }
+    if (sm > kTailSmemMax) return hipErrorInvalidValue;
     const dim3 grid(a.n * (a.H / (64 / a.W)));
-    if (a.step_mode == 2) ITSD_LAUNCH((tail2_kernel<T, true>), grid, dim3(256), sm, s, a);
-    else ITSD_LAUNCH(tail2_kernel<T>, grid, dim3(256), sm, s, a);
-    return hipGetLastError();
+    ITSD_RETURN_TAIL_LAUNCH(tail2_kernel<T>, (tail2_kernel<T, true>), true, grid, dim3(256), sm, s, a);
   }
   const long long total = (long long)a.n * a.H * a.W;
   const dim3 grid((unsigned)((total + 255) / 256));
-  if (a.step_mode == 2) ITSD_LAUNCH((tail_kernel<T, true>), grid, dim3(256), 27 * a.C * sizeof(float), s, a);
-  else ITSD_LAUNCH(tail_kernel<T>, grid, dim3(256), 27 * a.C * sizeof(float), s, a);
-  return hipGetLastError();
+  ITSD_RETURN_TAIL_LAUNCH(tail_kernel<T>, (tail_kernel<T, true>), false, grid, dim3(256), 27 * a.C * sizeof(float), s,
+                          a);
 }
 template hipError_t launch_tail<float>(const TailArgs&, hipStream_t);
 template hipError_t launch_tail<bf16_t>(const TailArgs&, hipStream_t);

@@ -165,7 +165,16 @@ int main() {
   expect("set_schedule null handle", itsd_set_schedule(nullptr, 4, f, f, f, 0.f), ITSD_ERR_INVALID);
   expect("sampler_run null handle", itsd_sampler_run(nullptr, f, nullptr, 1, 3, 0, 1, 0, nullptr, 0, nullptr),
          ITSD_ERR_INVALID);
-  expect("query null handle", itsd_unet_query(nullptr, "ops", &q), ITSD_ERR_INVALID);
+  expect("predict_x0 null handle", itsd_sampler_predict_x0(nullptr, f, nullptr, 1, 0, 1.f, 0.f, f + 8, nullptr),
+         ITSD_ERR_INVALID);
+  {  // a stand-in handle that must not be read: the null checks reject before anything looks at it
+    itsd_unet* h = reinterpret_cast<itsd_unet*>(ki);
+    expect("predict_x0 null x", itsd_sampler_predict_x0(h, nullptr, nullptr, 1, 0, 1.f, 0.f, f, nullptr),
+           ITSD_ERR_INVALID);
+    expect("predict_x0 null x0", itsd_sampler_predict_x0(h, f, nullptr, 1, 0, 1.f, 0.f, nullptr, nullptr),
+           ITSD_ERR_INVALID);
+  }
+  expect("query null handle",itsd_unet_query(nullptr, "ops", &q), ITSD_ERR_INVALID);
   expect("profile_forward null handle",
          itsd_profile_forward(nullptr, f, ti, 1, dd, dd, ki, dd, nullptr), ITSD_ERR_INVALID);
   expect("profile_ops null handle", itsd_profile_ops(nullptr, f, ti, 1, 4, ki, dd, dd, ki, ki, nullptr),
@@ -207,6 +216,37 @@ int main() {
   expect("noise n_cand=-1", itsd_noise(f, nullptr, -1, 16, 1.f, 0, 0, 0, nullptr), ITSD_ERR_INVALID);
   expect("noise per_cand=0", itsd_noise(f, nullptr, 1, 0, 1.f, 0, 0, 0, nullptr), ITSD_ERR_INVALID);
   expect("noise n_cand=0 (no-op)", itsd_noise(f, nullptr, 0, 16, 1.f, 0, 0, 0, nullptr), ITSD_OK);
+
+  // ---- itsd_branch: everything it rejects is rejected on the host, before a launch
+  {
+    float src[8] = {0}, dst[8] = {0};  // 2 candidates of 4 elements each
+    const int32_t par[2] = {1, 0};
+    auto branch = [&](float* d, const float* s, const int32_t* p, int n_src, int n_dst, int64_t per) {
+      return itsd_branch(d, s, p, n_src, n_dst, per, 1.f, 0.f, 0, 0, 0, nullptr);
+    };
+    expect("branch null dst", branch(nullptr, src, par, 2, 2, 4), ITSD_ERR_INVALID);
+    expect("branch null src", branch(dst, nullptr, par, 2, 2, 4), ITSD_ERR_INVALID);
+    expect("branch null parents", branch(dst, src, nullptr, 2, 2, 4), ITSD_ERR_INVALID);
+    expect("branch n_src=0", branch(dst, src, par, 0, 2, 4), ITSD_ERR_INVALID);
+    expect("branch n_dst=-1", branch(dst, src, par, 2, -1, 4), ITSD_ERR_INVALID);
+    expect("branch per_cand=0", branch(dst, src, par, 2, 2, 0), ITSD_ERR_INVALID);
+    expect("branch n_dst=0 (no-op)", branch(dst, src, par, 2, 0, 4), ITSD_OK);
+    const int32_t neg[2] = {0, -1}, big[2] = {2, 0};
+    expect("branch parent -1", branch(dst, src, neg, 2, 2, 4), ITSD_ERR_INVALID);
+    if (!std::strstr(itsd_last_error(), "parents[1] = -1")) {
+      std::printf("FAIL branch parent -1: message does not name the index (%s)\n", itsd_last_error());
+      ++g_fail;
+    }
+    expect("branch parent == n_src", branch(dst, src, big, 2, 2, 4), ITSD_ERR_INVALID);
+    if (!std::strstr(itsd_last_error(), "parents[0] = 2")) {
+      std::printf("FAIL branch parent == n_src: message does not name the index (%s)\n", itsd_last_error());
+      ++g_fail;
+    }
+    float both[12] = {0};  // dst = [0, 8), src = [4, 12) and the other way round: 4 elements shared
+    expect("branch dst overlaps src from below", branch(both, both + 4, par, 2, 2, 4), ITSD_ERR_INVALID);
+    expect("branch dst overlaps src from above", branch(both + 4, both, par, 2, 2, 4), ITSD_ERR_INVALID);
+    expect("branch dst == src", branch(both, both, par, 2, 2, 4), ITSD_ERR_INVALID);
+  }
 
   std::printf("%s (%d failures)\n", g_fail ? "FAILED" : "PASSED", g_fail);
   return g_fail ? 1 : 0;
