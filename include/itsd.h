@@ -30,6 +30,9 @@
  *   itsd_profile_forward / _ops / _op, itsd_unet_query, itsd_set_option
  *                                <- (no reference counterpart) per-kernel census used by
  *                                   bench.py for the roofline line, introspection, A/B switches
+ *   itsd_unet_op_info / _act_info / _read / _poison
+ *                                <- (no reference counterpart) introspection: a read-only probe of the op program
+ *                                   for the per-op parity tests (what each launch is, what it read and wrote)
  *
  * Conventions
  *  - Every tensor argument is a DEVICE pointer owned by the caller; the library
@@ -219,6 +222,73 @@ int itsd_set_option(const char* key, int value);
  * (0 ok; bit 0: attn_block_split_kernel's wait exhausted its bound, bit 1: conv3x3_gn_p5_kernel's shared split-K
  * combine -- ITSD_ERR_HANDOFF). */
 int itsd_unet_query(const itsd_unet* u, const char* key, int64_t* value);
+
+/* ---- Introspection of the op program (read-only; eager host code, nothing on the sampler's path).
+ * The per-op parity tests walk the program with these: describe an op, read what it read and wrote.
+ *
+ * Op indices are itsd_profile_ops' (1 = first program op .. "ops"); 0 is the head conv and "ops" + 1 the tail
+ * (GroupNorm + conv). Act ids index the handle's activation buffers (every op output has its own buffer; the
+ * channel-major V buffers are activations too, shaped H = C, W = S, C = 1); ITSD_ACT_PROJ is proj_buf, the
+ * [n][sumC] fp32 temb_proj rows of the last itsd_unet_forward. -1 = none. */
+enum { ITSD_OP_GN = 0, ITSD_OP_CONV = 1, ITSD_OP_ATTN = 2, ITSD_OP_GNCOEF = 3, ITSD_OP_ATTNBLOCK = 4,
+       ITSD_OP_HEAD = 5, ITSD_OP_TAIL = 6 };
+/* ops whose weights are not one state_dict tensor (itsd_op_info::tag) */
+enum { ITSD_TAG_NONE = 0,
+       ITSD_TAG_QKV = 1,         /* 1x1 conv over proj_q | proj_k | proj_v of the AttnBlock `name` */
+       ITSD_TAG_DOWN_MERGE = 2,  /* CFG DownSample `name`: c1 (3x3) + c2 (5x5) as one 5x5 conv */
+       ITSD_TAG_ATTN_S1 = 3,     /* one-token AttnBlock `name`: resid + proj(proj_v(src1)), src1 = its GroupNorm */
+       ITSD_TAG_CONVT = 4,       /* ConvTranspose2d(5, 2, 2, 1) `name` */
+       ITSD_TAG_ATTNBLOCK = 5 }; /* the fused AttnBlock `name` (GroupNorm, q|k|v, attention, proj, + x) */
+#define ITSD_ACT_PROJ (-2)
+typedef struct {
+  int32_t kind;                    /* ITSD_OP_* */
+  int32_t launched;                /* 1: run_program launches it at this batch / option state; 0: folded away */
+  int32_t folded_into;             /* launched == 0: the op (index) whose launch does this op's work */
+  int32_t src1, src2, dst, resid, vt;  /* act ids */
+  int32_t ksize, stride, pad, upsample, zins, subpix, Cout, K, temb_col, vt_from;  /* conv geometry as built */
+  int32_t silu;                    /* GN: SiLU applied */
+  int32_t S, C;                    /* attention kinds: tokens, width */
+  int32_t kernel;                  /* conv: the plan's ConvKernel enumerator (common.h order), else -1 */
+  int32_t ksplit, sc_split, kS;    /* conv: the plan's p5 K slices, folded-shortcut slices, conv_small / pipe slices */
+  int32_t epilogue;                /* conv: kS slices combined by a second launch (splitk_epilogue_kernel) */
+  int32_t gn_fold;                 /* conv: finalizes its input GroupNorm itself (its GNCOEF op is not launched) */
+  int32_t gn_out_op;               /* conv: the GN op (index) whose dst its epilogue writes, 0 none */
+  int32_t sc_op;                   /* conv with sc_split > 0: the shortcut op (index) it absorbs, else 0 */
+  int32_t has_coef;                /* GNCOEF / tail: writes a coef buffer; conv: its input GroupNorm is fused */
+  int32_t tag;                     /* ITSD_TAG_* */
+  char name[96];                   /* the state_dict prefix the op was built from, e.g. "downblocks.3.block2.3" */
+} itsd_op_info;
+typedef struct {
+  int32_t H, W, C;
+  int32_t elem_size;               /* bytes: 2 (bf16) or 4 */
+  int32_t has_stats;               /* a GroupNorm statistics slab [n * spi][2][C] fp32 belongs to it */
+  int32_t spi;                     /* its slots per image (stat_spi: HW / min(HW, 128), or 4 phases) */
+  int32_t capacity;                /* images the buffer holds */
+} itsd_act_info;
+/* What program op `op_index` is and how it would run at batch n under the current options: resolved exactly as
+ * the pass resolves it -- ITSD_PASS_FORWARD: itsd_unet_forward; ITSD_PASS_STEP: the sampler step of
+ * itsd_sampler_run / itsd_sampler_predict_x0, whose program runs 2n images for CFG (cond || uncond: image i >= n
+ * reads x[i - n] and label 0, and the tail combines the halves). No launch, no device call. ITSD_ERR_INVALID: null
+ * u / info, unknown pass, op_index outside [0, ops + 1], n outside [1, max_batch]. */
+enum { ITSD_PASS_FORWARD = 0, ITSD_PASS_STEP = 1 };
+int itsd_unet_op_info(itsd_unet* u, int pass, int n, int op_index, itsd_op_info* info);
+/* ITSD_ERR_INVALID: null u / info, act neither ITSD_ACT_PROJ nor in [0, acts). No device call. */
+int itsd_unet_act_info(const itsd_unet* u, int act, itsd_act_info* info);
+/* Stream-ordered device-to-device copy of raw buffer contents (no conversion) into dst (device, `bytes` long):
+ * ITSD_READ_ACT: the first n images of activation `id` (n H W C elements); ITSD_READ_STATS: its statistics slab
+ * (n spi 2 C fp32); ITSD_READ_COEF: the coef buffer [n][Cin/8][a0..a7, b0..b7] fp32 of GNCOEF op `id` (or of the
+ * tail, id = ops + 1); ITSD_READ_PROJ: proj_buf (n sumC fp32; id ignored). ITSD_ERR_INVALID before any HIP call:
+ * null u / dst, unknown what, id out of range or without such a buffer, n outside [1, capacity], bytes != the
+ * size above. */
+enum { ITSD_READ_ACT = 0, ITSD_READ_STATS = 1, ITSD_READ_COEF = 2, ITSD_READ_PROJ = 3 };
+int itsd_unet_read(itsd_unet* u, int what, int id, int n, void* dst, int64_t bytes, void* stream);
+/* Fill every buffer a forward overwrites completely with NaN bits (bf16 0xFFFF, fp32 0xFFFFFFFF), stream-ordered:
+ * the activation arena (activations, channel-major V, coef buffers and the statistics slabs -- every producer
+ * stores its slots plainly, none accumulates) and the split-K workspace. Left alone: what the program increments or
+ * needs zero between launches (split-K tickets, the AttnBlock hand-off counters, the NaN / status words, the zero
+ * page), the weights, proj_buf and the embedding tables. A forward afterwards must give the bits it gives on a fresh
+ * handle: a NaN or a changed value means a launch read something no launch of that forward wrote. */
+int itsd_unet_poison(itsd_unet* u, void* stream);
 
 /* Name of census kernel id `id` (itsd_profile_ops): the launch site's kernel expression,
  * e.g. "conv3x3_gn_p4_kernel<32>"; "" for 0 / unknown ids. */

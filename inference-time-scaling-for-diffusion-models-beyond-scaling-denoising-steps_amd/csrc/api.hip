@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <functional>
 #include <map>
@@ -140,6 +141,10 @@ struct Op {
   // a conv and the GroupNorm op right after it over its output alone (conv_small writes the GroupNorm's output in its
   // epilogue, ConvArgs gn_out): on the conv, the GN op; on the GN op, the conv
   int gn_next = -1, gn_from = -1;
+  // introspection (itsd_unet_op_info): the state_dict prefix the op was built from, and ITSD_TAG_* where its weights
+  // are not one state_dict tensor
+  std::string name;
+  int tag = ITSD_TAG_NONE;
 };
 
 // Host staging for the weight arena: fp32 params and packed conv weights.
@@ -399,6 +404,7 @@ struct Builder {
     if (A.H * A.W < 128) u->acts[dst].spi = 4;  // one statistics slot per (image, phase)
     conv(s1, -1, dst, wt, b, Cout, 3, 1, 1, 1);
     Op& o = u->ops.back();
+    o.name = name;
     o.subpix = 1;
     o.wfrag = wf;
     return dst;
@@ -425,6 +431,7 @@ struct Builder {
     o.gamma = f32(p + ".weight", C);
     o.beta = f32(p + ".bias", C);
     o.silu = silu;
+    o.name = p;
     u->ops.push_back(o);
   }
   void conv(int s1, int s2, int dst, size_t wt, size_t bias, int Cout, int ks, int stride, int pad, int ups,
@@ -452,6 +459,7 @@ struct Builder {
       g.gamma = f32(gn + ".weight", Cin);
       g.beta = f32(gn + ".bias", Cin);
       g.coef = coef = ws_off;
+      g.name = gn;
       ws_off = (ws_off + (size_t)u->nb_max * Cin * 2 * 4 + 255) & ~(size_t)255;
       u->ops.push_back(g);
     }
@@ -482,6 +490,7 @@ struct Builder {
     size_t b = bx ? ar.add(bx, (size_t)Cout * 4) : f32(name + ".bias", Cout);
     int dst = act(Hout, Wout, Cout);
     conv(s1, s2, dst, wt, b, Cout, ks, stride, pad, ups, temb_col, resid);
+    u->ops.back().name = name;
     u->ops.back().coef = coef;
     if (coef != SIZE_MAX) {  // (the GNCOEF op pushed just before this conv)
       u->ops.back().gn_gamma = u->ops[u->ops.size() - 2].gamma;
@@ -576,7 +585,10 @@ struct Builder {
         }
         int ga = act(H, W, out_ch);
         gn(o, -1, ga, a + ".group_norm", out_ch, 0);
-        return conv_layer(ga, -1, a + ".proj", out_ch, 1, 1, 0, 0, H, W, -1, o, "", wf.data(), bf.data());
+        const int r = conv_layer(ga, -1, a + ".proj", out_ch, 1, 1, 0, 0, H, W, -1, o, "", wf.data(), bf.data());
+        u->ops.back().name = a;
+        u->ops.back().tag = ITSD_TAG_ATTN_S1;
+        return r;
       }
     }
     if (attn && u->bf16 && itsd::g_attn_fuse && attn_block_ok(H * W, out_ch)) {
@@ -605,6 +617,8 @@ struct Builder {
       ab.S = H * W;
       ab.C = out_ch;
       ab.dst = act(H, W, out_ch);
+      ab.name = a;
+      ab.tag = ITSD_TAG_ATTNBLOCK;
       u->ops.push_back(ab);
       return ab.dst;
     }
@@ -619,6 +633,8 @@ struct Builder {
                                 get(a + ".proj_v.bias", out_ch)}, out_ch);
       int qkv = act(H, W, 3 * out_ch);
       conv(ga, -1, qkv, wqkv, bqkv, 3 * out_ch, 1, 1, 0, 0);
+      u->ops.back().name = a;
+      u->ops.back().tag = ITSD_TAG_QKV;
       // MFMA attention (bf16): V goes channel-major to its own buffer from the conv epilogue
       const int S = H * W;
       int vt = -1;
@@ -631,6 +647,7 @@ struct Builder {
       int ao = act(H, W, out_ch);
       Op at;
       at.kind = OP_ATTN;
+      at.name = a;
       at.src1 = qkv; at.dst = ao; at.S = H * W; at.C = out_ch; at.vt = vt;
       u->ops.push_back(at);
       o = conv_layer(ao, -1, a + ".proj", out_ch, 1, 1, 0, 0, H, W, -1, o);
@@ -721,6 +738,8 @@ int build(itsd_unet* u, const itsd_tensor_view* views, int nviews) {
               for (int kx = 0; kx < 3; ++kx) wm[(oc * 5 + ky + 1) * 5 + kx + 1] += W1[(oc * 3 + ky) * 3 + kx];
         for (int c = 0; c < now; ++c) bm[c] = (b1 ? b1[c] : 0.f) + (b2 ? b2[c] : 0.f);
         cur = b.conv_layer(cur, -1, p + ".c12", now, 5, 2, 2, 0, Hc / 2, Hc / 2, -1, -1, "", wm.data(), bm.data());
+        u->ops.back().name = p;
+        u->ops.back().tag = ITSD_TAG_DOWN_MERGE;
       }
       hs.push_back(cur);
     }
@@ -762,9 +781,13 @@ int build(itsd_unet* u, const itsd_tensor_view* views, int nviews) {
           b.conv(cur, -1, tmp, wt, bt, now, c1 ? 1 : 3, 1, c1 ? 0 : 1, 0);
           u->ops.back().subpix = 2;
           u->ops.back().wfrag = wf;
+          u->ops.back().name = p + ".t";
+          u->ops.back().tag = ITSD_TAG_CONVT;
         } else {
           size_t wt = b.pack({Wt}, now, now, 5, true);
           b.conv(cur, -1, tmp, wt, bt, now, 5, 1, 2, 0, -1, -1, 1);
+          u->ops.back().name = p + ".t";
+          u->ops.back().tag = ITSD_TAG_CONVT;
         }
         cur = b.conv_layer(tmp, -1, p + ".c", now, 3, 1, 1, 0, 2 * Hc, 2 * Hc);
       }
@@ -1030,6 +1053,19 @@ std::vector<ConvLaunch> resolve_program(itsd_unet* u, const RunCtx& c) {
   return r;
 }
 
+// The op (index in u->ops) whose launch does op oi's work, or -1 where op oi is launched itself: what run_program
+// skips and itsd_unet_op_info reports. A conv whose conv_args failed folds nothing and fails at its turn.
+int folded_into(const itsd_unet* u, const std::vector<ConvLaunch>& rp, size_t oi) {
+  const Op& o = u->ops[oi];
+  // gn_fold: the consumer conv finalizes this GroupNorm itself
+  if (o.kind == OP_GNCOEF && oi + 1 < u->ops.size() && rp[oi + 1].a.gn_fold) return (int)oi + 1;
+  // a GroupNorm its producer conv wrote in its epilogue
+  if (o.kind == OP_GN && o.gn_from >= 0 && rp[o.gn_from].a.gn_out) return o.gn_from;
+  // a shortcut its block2 conv runs as K slices
+  if (o.kind == OP_CONV && o.sc_into >= 0 && rp[o.sc_into].p.sc_split) return o.sc_into;
+  return -1;
+}
+
 // What both GroupNorm op kinds read: the (concatenated) input's channels, its statistics slabs, gamma / beta.
 GNArgs gn_args(const itsd_unet* u, const Op& o) {
   GNArgs g{};
@@ -1159,13 +1195,7 @@ int run_program(itsd_unet* u, const RunCtx& c, const std::vector<ConvLaunch>& rp
   // census kinds: OpKind, and kCensusConvGN for the fused GroupNorm+SiLU convs
   for (size_t oi = 0; oi < u->ops.size(); ++oi) {
     const Op& o = u->ops[oi];
-    // launches folded into a neighbouring conv's (a conv whose conv_args failed folds nothing and fails at its turn):
-    // gn_fold: the consumer conv finalizes this GroupNorm itself
-    if (o.kind == OP_GNCOEF && oi + 1 < u->ops.size() && rp[oi + 1].a.gn_fold) continue;
-    // a GroupNorm its producer conv wrote in its epilogue
-    if (o.kind == OP_GN && o.gn_from >= 0 && rp[o.gn_from].a.gn_out) continue;
-    // a shortcut its block2 conv runs as K slices
-    if (o.kind == OP_CONV && o.sc_into >= 0 && rp[o.sc_into].p.sc_split) continue;
+    if (folded_into(u, rp, oi) >= 0) continue;
     const ConvLaunch& cl = rp[oi];
     int kind = o.kind == OP_ATTNBLOCK ? kCensusAttnBlock : (int)o.kind;
     cur_op = (int)oi + 1;
@@ -1893,6 +1923,142 @@ int itsd_profile_ops(itsd_unet* u, const float* x, const int32_t* t, int n, int 
   }
   *n_ops = k;
   return ITSD_OK;
+}
+
+// ---- introspection of the op program (include/itsd.h): eager host code beside the program, nothing on its path
+int itsd_unet_op_info(itsd_unet* u, int pass, int n, int op_index, itsd_op_info* info) {
+  if (!u || !info) return fail(ITSD_ERR_INVALID, "null argument");
+  if (pass != ITSD_PASS_FORWARD && pass != ITSD_PASS_STEP) return fail(ITSD_ERR_INVALID, "op_info: unknown pass");
+  const int nops = (int)u->ops.size();
+  if (op_index < 0 || op_index > nops + 1)
+    return fail(ITSD_ERR_INVALID, "op_info: op_index outside [0, ops + 1 = " + std::to_string(nops + 1) + "]");
+  CHK(check_batch(u, n));
+  itsd_op_info r;
+  std::memset(&r, 0, sizeof(r));
+  r.launched = 1;
+  r.src1 = r.src2 = r.dst = r.resid = r.vt = r.temb_col = r.kernel = -1;
+  auto name = [&r](const std::string& s) { std::snprintf(r.name, sizeof(r.name), "%s", s.c_str()); };
+  if (op_index == 0) {
+    r.kind = ITSD_OP_HEAD;
+    r.dst = u->head_out;
+    r.ksize = 3; r.stride = 1; r.pad = 1; r.Cout = u->ch; r.K = 27;
+    name("head");
+  } else if (op_index == nops + 1) {
+    r.kind = ITSD_OP_TAIL;
+    r.src1 = u->tail_in;
+    r.dst = u->tail_g;  // (the plain tail's GroupNorm output; -1: fused into tail_mfma_kernel through the coef buffer)
+    r.has_coef = u->tail_wmf != SIZE_MAX;
+    r.silu = 1;
+    r.ksize = 3; r.stride = 1; r.pad = 1; r.Cout = 3; r.K = 9 * u->acts[u->tail_in].C;
+    name("tail");
+  } else {
+    // a throw-away pass context: what itsd_unet_forward, or the sampler step (itsd_sampler_run / _predict_x0: the
+    // doubled cond||uncond batch for CFG), resolves at this batch (no pointer in it is followed)
+    const RunCtx c = pass == ITSD_PASS_STEP ? step_ctx(u, n, nullptr, nullptr) : forward_ctx(u, n, nullptr, nullptr, nullptr);
+    const std::vector<ConvLaunch> rp = resolve_program(u, c);
+    const int oi = op_index - 1;
+    const Op& o = u->ops[oi];
+    r.kind = o.kind == OP_GN ? ITSD_OP_GN : o.kind == OP_CONV ? ITSD_OP_CONV : o.kind == OP_ATTN ? ITSD_OP_ATTN
+             : o.kind == OP_GNCOEF ? ITSD_OP_GNCOEF : ITSD_OP_ATTNBLOCK;
+    r.src1 = o.src1; r.src2 = o.src2; r.dst = o.dst; r.resid = o.resid; r.vt = o.vt;
+    r.silu = o.silu;
+    r.S = o.S; r.C = o.C;
+    r.tag = o.tag;
+    name(o.name);
+    if (const int into = folded_into(u, rp, (size_t)oi); into >= 0) { r.launched = 0; r.folded_into = into + 1; }
+    if (o.kind == OP_GNCOEF) r.has_coef = 1;
+    if (o.kind == OP_CONV) {
+      const ConvLaunch& cl = rp[oi];
+      if (cl.rc != ITSD_OK) return fail(cl.rc, cl.err);
+      r.ksize = o.ksize; r.stride = o.stride; r.pad = o.pad; r.upsample = o.upsample; r.zins = o.zins;
+      r.subpix = o.subpix; r.Cout = o.Cout; r.K = o.K; r.temb_col = o.temb_col; r.vt_from = o.vt_from;
+      r.kernel = (int)cl.p.kernel;
+      r.ksplit = cl.p.ksplit; r.sc_split = cl.p.sc_split; r.kS = cl.p.S;
+      r.epilogue = cl.p.epilogue ? 1 : 0;
+      r.gn_fold = cl.a.gn_fold;
+      r.gn_out_op = cl.a.gn_out ? o.gn_next + 1 : 0;
+      r.sc_op = cl.p.sc_split ? o.sc_op + 1 : 0;
+      r.has_coef = o.coef != SIZE_MAX;
+    }
+  }
+  *info = r;
+  return ITSD_OK;
+}
+
+int itsd_unet_act_info(const itsd_unet* u, int act, itsd_act_info* info) {
+  if (!u || !info) return fail(ITSD_ERR_INVALID, "null argument");
+  itsd_act_info r;
+  std::memset(&r, 0, sizeof(r));
+  if (act == ITSD_ACT_PROJ) {
+    r.H = r.W = 1; r.C = u->sumC; r.elem_size = 4; r.capacity = u->d.max_batch;
+  } else {
+    if (act < 0 || act >= (int)u->acts.size())
+      return fail(ITSD_ERR_INVALID, "act_info: act outside [0, " + std::to_string(u->acts.size()) + ")");
+    const Act& A = u->acts[act];
+    r.H = A.H; r.W = A.W; r.C = A.C; r.elem_size = (int)u->esz; r.capacity = u->nb_max;
+    r.has_stats = A.stats != SIZE_MAX;
+    r.spi = stat_spi(A.H * A.W, A.spi);
+  }
+  *info = r;
+  return ITSD_OK;
+}
+
+int itsd_unet_read(itsd_unet* u, int what, int id, int n, void* dst, int64_t bytes, void* stream) {
+  if (!u || !dst) return fail(ITSD_ERR_INVALID, "null argument");
+  const char* src = nullptr;
+  int64_t want = 0;
+  int cap = u->nb_max;
+  if (what == ITSD_READ_ACT || what == ITSD_READ_STATS) {
+    if (id < 0 || id >= (int)u->acts.size())
+      return fail(ITSD_ERR_INVALID, "read: act outside [0, " + std::to_string(u->acts.size()) + ")");
+    const Act& A = u->acts[id];
+    if (what == ITSD_READ_ACT) {
+      src = u->ws + A.off;
+      want = (int64_t)A.H * A.W * A.C * (int64_t)u->esz;
+    } else {
+      if (A.stats == SIZE_MAX) return fail(ITSD_ERR_INVALID, "read: activation " + std::to_string(id) + " has no statistics slab");
+      src = u->ws + A.stats;
+      want = (int64_t)stat_spi(A.H * A.W, A.spi) * 2 * A.C * 4;
+    }
+  } else if (what == ITSD_READ_COEF) {
+    const int nops = (int)u->ops.size();
+    if (id == nops + 1 && u->tail_coef != SIZE_MAX) {
+      src = u->ws + u->tail_coef;
+      want = (int64_t)u->acts[u->tail_in].C * 2 * 4;
+    } else if (id >= 1 && id <= nops && u->ops[id - 1].kind == OP_GNCOEF) {
+      const Op& o = u->ops[id - 1];
+      src = u->ws + o.coef;
+      want = (int64_t)(u->acts[o.src1].C + (o.src2 >= 0 ? u->acts[o.src2].C : 0)) * 2 * 4;
+    } else {
+      return fail(ITSD_ERR_INVALID, "read: op " + std::to_string(id) + " has no coef buffer");
+    }
+  } else if (what == ITSD_READ_PROJ) {
+    src = (const char*)u->proj_buf;
+    want = (int64_t)u->sumC * 4;
+    cap = u->d.max_batch;
+  } else {
+    return fail(ITSD_ERR_INVALID, "read: unknown buffer class " + std::to_string(what));
+  }
+  if (n < 1 || n > cap) return fail(ITSD_ERR_INVALID, "read: n outside [1, " + std::to_string(cap) + "]");
+  want *= n;
+  if (bytes != want)
+    return fail(ITSD_ERR_INVALID, "read: bytes = " + std::to_string(bytes) + ", the buffer holds " + std::to_string(want));
+  hipStream_t cs = (hipStream_t)stream;
+  CHK(enter_stream(u, cs));
+  HIPCHK(hipMemcpyAsync(dst, src, (size_t)want, hipMemcpyDeviceToDevice, u->stream));
+  return leave_stream(u, cs);
+}
+
+int itsd_unet_poison(itsd_unet* u, void* stream) {
+  if (!u) return fail(ITSD_ERR_INVALID, "null argument");
+  hipStream_t cs = (hipStream_t)stream;
+  CHK(enter_stream(u, cs));
+  // the arena holds activations, channel-major V, coef buffers and statistics slabs only (Builder::act, conv_layer,
+  // build): all of them stored whole by their producers
+  HIPCHK(hipMemsetAsync(u->ws, 0xFF, u->ws_bytes, u->stream));
+  HIPCHK(hipMemsetAsync(u->splitk_ws, 0xFF, (size_t)itsd_unet::kSplitkCap * 4, u->stream));
+  u->last_forward_n = 0;  // (the tail input is gone: itsd_unet_representation refuses until the next forward)
+  return leave_stream(u, cs);
 }
 
 }  // extern "C"

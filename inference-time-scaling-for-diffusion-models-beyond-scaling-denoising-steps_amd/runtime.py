@@ -42,6 +42,29 @@ class TensorView(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char_p), ("data", ctypes.c_void_p), ("numel", ctypes.c_int64)]
 
 
+class OpInfo(ctypes.Structure):
+    """itsd_op_info (include/itsd.h)."""
+    _fields_ = [(k, ctypes.c_int32) for k in (
+        "kind", "launched", "folded_into", "src1", "src2", "dst", "resid", "vt", "ksize", "stride", "pad", "upsample",
+        "zins", "subpix", "Cout", "K", "temb_col", "vt_from", "silu", "S", "C", "kernel", "ksplit", "sc_split", "kS",
+        "epilogue", "gn_fold", "gn_out_op", "sc_op", "has_coef", "tag")] + [("name", ctypes.c_char * 96)]
+
+
+class ActInfo(ctypes.Structure):
+    """itsd_act_info (include/itsd.h)."""
+    _fields_ = [(k, ctypes.c_int32) for k in ("H", "W", "C", "elem_size", "has_stats", "spi", "capacity")]
+
+
+OP_GN, OP_CONV, OP_ATTN, OP_GNCOEF, OP_ATTNBLOCK, OP_HEAD, OP_TAIL = range(7)
+OP_KINDS = ("gn", "conv", "attn", "gncoef", "attnblock", "head", "tail")
+TAG_NONE, TAG_QKV, TAG_DOWN_MERGE, TAG_ATTN_S1, TAG_CONVT, TAG_ATTNBLOCK = range(6)
+# ConvKernel (csrc/common.h), in its order
+CONV_KERNELS = ("P5", "P5_SHARED", "P4_GN", "P4_C96", "P4_PLAIN", "P4_SUB", "P4_CONVT", "GN128", "STREAM1X1", "SMALL",
+                "PIPE_LIN", "PIPE", "PIPE_SUBPIX", "IGEMM")
+ACT_PROJ = -2
+READ_ACT, READ_STATS, READ_COEF, READ_PROJ = range(4)
+PASS_FORWARD, PASS_STEP = 0, 1
+
 _lib = None
 
 _SIGS = {
@@ -79,6 +102,11 @@ _SIGS = {
     "itsd_set_option": [ctypes.c_char_p, ctypes.c_int],
     "itsd_calibrate": [ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_void_p],
     "itsd_unet_query": [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64)],
+    "itsd_unet_op_info": [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(OpInfo)],
+    "itsd_unet_act_info": [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ActInfo)],
+    "itsd_unet_read": [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
+                       ctypes.c_void_p],
+    "itsd_unet_poison": [ctypes.c_void_p, ctypes.c_void_p],
     "itsd_kernel_name": [ctypes.c_int],
     "itsd_last_error": [],
     "itsd_version": [],
@@ -251,6 +279,56 @@ class NativeUNet:
                  "resid": bool(sh[i, 7] & 1), "stats_out": bool(sh[i, 7] & 2), "gn_in": bool(sh[i, 7] & 4),
                  "sc_cin": int(sh[i, 7]) >> 8}
                 for i in range(k)]
+
+    # ---- the read-only probe of the op program (itsd_unet_op_info / _act_info / _read / _poison)
+    def op_info(self, n: int, op_index: int, step: bool = False) -> dict:
+        """Program op `op_index` (profile_ops numbering; 0 the head, query("ops") + 1 the tail) as it would run at
+        batch n under the current options in a forward, or (step) in the sampler step, whose CFG program runs 2n
+        images: a dict of itsd_op_info's fields, with "kind" and "kernel" as names."""
+        info = OpInfo()
+        check(lib().itsd_unet_op_info(self.h, PASS_STEP if step else PASS_FORWARD, int(n), int(op_index),
+                                      ctypes.byref(info)))
+        d = {k: getattr(info, k) for k, _ in OpInfo._fields_}
+        d["name"] = info.name.decode()
+        d["kind"] = OP_KINDS[info.kind]
+        d["kernel"] = CONV_KERNELS[info.kernel] if info.kernel >= 0 else ""
+        d["op"] = int(op_index)
+        return d
+
+    def act_info(self, act: int) -> dict:
+        info = ActInfo()
+        check(lib().itsd_unet_act_info(self.h, int(act), ctypes.byref(info)))
+        return {k: getattr(info, k) for k, _ in ActInfo._fields_}
+
+    def _read(self, what: int, ident: int, n: int, out: torch.Tensor) -> torch.Tensor:
+        check(lib().itsd_unet_read(self.h, int(what), int(ident), int(n), out.data_ptr(),
+                                   out.numel() * out.element_size(), stream_ptr(out.device)))
+        return out
+
+    def read_act(self, act: int, n: int, device="cuda") -> torch.Tensor:
+        """The first n images of activation `act`, raw: [n, H, W, C] in the handle's storage type."""
+        a = self.act_info(act)
+        dt = torch.bfloat16 if a["elem_size"] == 2 else torch.float32
+        return self._read(READ_ACT, act, n, torch.empty(n, a["H"], a["W"], a["C"], dtype=dt, device=device))
+
+    def read_stats(self, act: int, n: int, device="cuda") -> torch.Tensor:
+        """The statistics slab of `act`: [n, spi, 2, C] fp32 (sum, sum of squares per slot and channel)."""
+        a = self.act_info(act)
+        return self._read(READ_STATS, act, n, torch.empty(n, a["spi"], 2, a["C"], dtype=torch.float32, device=device))
+
+    def read_coef(self, op_index: int, n: int, channels: int, device="cuda") -> torch.Tensor:
+        """The coef buffer of GNCOEF op `op_index` (or the tail's): [n, channels / 8, 2, 8] fp32 (a0..a7, b0..b7)."""
+        return self._read(READ_COEF, op_index, n,
+                          torch.empty(n, channels // 8, 2, 8, dtype=torch.float32, device=device))
+
+    def read_proj(self, n: int, device="cuda") -> torch.Tensor:
+        """proj_buf of the last forward: [n, sumC] fp32 (every ResBlock's temb_proj row, side by side)."""
+        a = self.act_info(ACT_PROJ)
+        return self._read(READ_PROJ, 0, n, torch.empty(n, a["C"], dtype=torch.float32, device=device))
+
+    def poison(self, device=None) -> None:
+        """NaN bits into every buffer a forward overwrites completely (itsd_unet_poison)."""
+        check(lib().itsd_unet_poison(self.h, stream_ptr(device)))
 
 
 def noise(out: torch.Tensor, n_cand: int, seed: int, stream_id: int, cand_offset: int = 0,

@@ -181,6 +181,24 @@ int main() {
          ITSD_ERR_INVALID);
   expect("profile_op null handle", itsd_profile_op(nullptr, f, ti, 1, 1, 1, dd, nullptr), ITSD_ERR_INVALID);
 
+  // ---- the op-program probe: null handle / output before anything is read; the range and byte-count checks need a
+  // handle and run on the GPU (tests/test_gpu_ops.py)
+  {
+    itsd_op_info oi;
+    itsd_act_info ai;
+    itsd_unet* h = reinterpret_cast<itsd_unet*>(ki);  // a stand-in handle that must not be read
+    expect("op_info null handle", itsd_unet_op_info(nullptr, ITSD_PASS_FORWARD, 1, 1, &oi), ITSD_ERR_INVALID);
+    expect("op_info null info", itsd_unet_op_info(h, ITSD_PASS_STEP, 1, 1, nullptr), ITSD_ERR_INVALID);
+    expect("act_info null handle", itsd_unet_act_info(nullptr, 0, &ai), ITSD_ERR_INVALID);
+    expect("act_info null info", itsd_unet_act_info(h, 0, nullptr), ITSD_ERR_INVALID);
+    expect("act_info null handle, proj", itsd_unet_act_info(nullptr, ITSD_ACT_PROJ, &ai), ITSD_ERR_INVALID);
+    expect("read null handle", itsd_unet_read(nullptr, ITSD_READ_ACT, 0, 1, f, 64, nullptr), ITSD_ERR_INVALID);
+    expect("read null dst", itsd_unet_read(h, ITSD_READ_ACT, 0, 1, nullptr, 64, nullptr), ITSD_ERR_INVALID);
+    expect("read null handle, bytes=0", itsd_unet_read(nullptr, ITSD_READ_PROJ, 0, 1, f, 0, nullptr), ITSD_ERR_INVALID);
+    expect("read null handle, what=9", itsd_unet_read(nullptr, 9, 0, 1, f, 64, nullptr), ITSD_ERR_INVALID);
+    expect("poison null handle", itsd_unet_poison(nullptr, nullptr), ITSD_ERR_INVALID);
+  }
+
   // ---- itsd_verify
   expect("verify null images", itsd_verify(0, nullptr, 1, 1, 3, 32, 32, dd, nullptr), ITSD_ERR_INVALID);
   expect("verify null scores", itsd_verify(0, f, 1, 1, 3, 32, 32, nullptr, nullptr), ITSD_ERR_INVALID);
