@@ -87,7 +87,8 @@ typedef struct {
   int32_t n_attn;
   int32_t attn[8];         /* 'attn' level indices (DDPM only) */
   int32_t num_res_blocks;
-  int32_t img_size;        /* H = W */
+  int32_t img_size;        /* H = W: divisible by 2^(n_mult - 1); every level's H*W divides or is a multiple of 128
+                              (else create answers ITSD_ERR_INVALID: 8, 16, 32, 64, 128, 256 px hold) */
   int32_t num_labels;      /* CFG only */
   int32_t max_batch;       /* largest n passed to forward/sampler (CFG: per-branch n) */
   int32_t precision;       /* ITSD_PREC_FP32 (parity) or ITSD_PREC_BF16 (throughput) */

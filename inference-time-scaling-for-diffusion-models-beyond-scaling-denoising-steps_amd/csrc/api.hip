@@ -696,6 +696,13 @@ int build(itsd_unet* u, const itsd_tensor_view* views, int nviews) {
         for (int k = 0; k < 27; ++k) wm[(size_t)co * 32 + k] = host_f2bf(hw[(size_t)co * 27 + k]);
       u->head_wmf = b.ar.add(wm.data(), wm.size() * 2);
     }
+  } else {
+    // the plain head kernel's blocks are one statistics slot of whole rows, or a segment of one row (launch_head):
+    // refused here, not at the first forward
+    const int G = stat_slot_px(H * H);
+    if ((H * H) % G || (G % H && H % G))
+      return fail(ITSD_ERR_INVALID, "img_size " + std::to_string(H) + " not supported by the head kernel (its " +
+                                        std::to_string(G) + "-pixel blocks hold whole rows or lie inside one)");
   }
 
   std::vector<int> hs{u->head_out};

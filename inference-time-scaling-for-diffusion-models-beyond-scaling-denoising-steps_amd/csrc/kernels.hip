@@ -1581,7 +1581,8 @@ template <typename T>
 hipError_t launch_head(const HeadArgs& a, hipStream_t s) {
   constexpr int EPC = 16 / (int)sizeof(T);
   const int HW = a.H * a.W, G = stat_slot_px(HW), cq = a.Cout / EPC;
-  if (a.Cout % EPC || cq > 256 || 256 % cq || HW % G || (G % a.W && a.W % G)) return hipErrorInvalidValue;
+  // (cq need not divide 256 -- Cout = 96: the kernel idles the threads past plan = 256 / cq whole pixel lanes)
+  if (a.Cout % EPC || cq > 256 || HW % G || (G % a.W && a.W % G)) return hipErrorInvalidValue;
   const int TW = (a.W <= G ? a.W : G) + 2, TR = (a.W <= G ? G / a.W : 1) + 2;
   const size_t smem = ((size_t)a.Cout * 28 + (size_t)(256 / cq) * a.Cout * 2 + 3 * TR * TW) * sizeof(float);
   ITSD_LAUNCH(head_kernel<T>, dim3((unsigned)((long long)a.n * HW / G)), dim3(256), smem, s, a);

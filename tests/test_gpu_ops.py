@@ -37,7 +37,10 @@ Acceptance (DESIGN.md "Parity", per-op rule). ref = the fp64 result; S = the sam
                        from the fp64 conv(silu(GN)) of both halves; the eps bounds through the combination and b0
 
 The image subset holds images 0 and n - 1 and both sides of the tile seams of the levels involved (8x8: four images
-a 256-pixel tile; 4x4: eight a 128-pixel tile).
+a 256-pixel tile; 4x4: eight a 128-pixel tile). The geometry cases (GEOMETRY_CASES) compare every image up to n = 8, and
+at n = 37 both sides of the 16- and 32-image seams of the 2x2 / 1x1 levels' tiles.
+
+An op kind or tag the walker does not know raises (KeyError / AssertionError in walk): the case fails, nothing is skipped.
 """
 import dataclasses
 import functools
@@ -51,7 +54,7 @@ import torch.nn.functional as F
 from conftest import GOLDEN
 from oracle import ref_cpu as R
 from itsd import runtime as rt
-from itsd.arch import ARCH_A, ARCH_C, ARCH_TINY, ARCH_TINY_CFG
+from itsd.arch import ARCH_A, ARCH_C, ARCH_CFG, ARCH_TINY, ARCH_TINY_CFG, UNetArch
 from itsd.weights import synthetic_state_dict
 
 pytestmark = pytest.mark.gpu
@@ -64,7 +67,7 @@ ARCH_A64 = dataclasses.replace(ARCH_A, img_size=64)
 # shipped values of the options the cases switch (csrc/conv.hip, kernels.hip, api.hip)
 DEFAULTS = {"gn_wide": 1, "p5_sc": 1, "p5_split": 0, "p5_dist": 1, "p5_pub": 1, "gn_fold": 1, "splitk": 1, "p4_sub": 1,
             "conv_variant": 2, "attn_split": 1, "small_gn": 1, "convt_prune": 1, "p5": 1, "p4_c96": 1,
-            "splitk_inl": 1, "io_mfma": 1, "attn_fuse": 1}
+            "splitk_inl": 1, "io_mfma": 1, "attn_fuse": 1, "attn_wide": 1, "attn_wide_nq": 1}
 
 
 @dataclasses.dataclass(frozen=True)
@@ -94,6 +97,8 @@ CASES = [
     _A(16, ("p5_split", 3), ("p5_dist", 1)), _A(16, ("p5_split", 3), ("p5_dist", 0)), _A(13, ("p5_pub", 0)),
     _A(13, ("gn_fold", 0)), _A(13, ("splitk", 0)), _A(256, ("p4_sub", 0), sub=(0, 3, 4, 255)),
     _A(13, ("conv_variant", 1)), _A(16, ("attn_split", 0)), _A(16, ("attn_split", 4)),
+    # (attn_block_split_kernel<384, 2>: auto takes 6 blocks an image up to n = 42, 4 up to 64, 2 up to 128)
+    _A(16, ("attn_split", 2)),
     # conv_pipe's split-K combined by splitk_epilogue_kernel (a conv's second launch: the census never names it)
     _A(13, ("splitk_inl", 0)),
     # the create-time alternatives: the plain bf16 head / tail kernels, the unfused AttnBlock at S = 64
@@ -114,6 +119,58 @@ CASES = [
     Case("A-fp32-n3", ARCH_A, "fp32", 3),
     Case("tinycfg-fp32-n3", ARCH_TINY_CFG, "fp32", 3),
 ]
+
+# Geometries outside the shipped configurations (itsd_unet_create takes any ch % 32 == 0, ch_mult, attn,
+# num_res_blocks and any img_size the statistics slots hold): the shapes on which the Builder's and plan_conv's
+# divisibility predicates choose differently -- channel counts that are no multiple of 64 / 128, GroupNorm groups
+# narrower than a 16-byte chunk, the AttnBlock and attention instantiations Arch A / C never launch, the DDPM model at
+# the 2x2 and 1x1 levels. Shipped options unless the id says otherwise; n <= 8 compares every image, n = 37 both sides
+# of the 16- and 32-image seams (a 128-pixel tile of a 2x2 level holds 32 images, a 64-pixel tile 16).
+_G = lambda **kw: UNetArch(**kw)
+ARCH_CFG96 = _G(ch=32, ch_mult=(1, 3), attn=(), num_res_blocks=1, kind=ARCH_CFG)
+ARCH_CH64 = _G(ch=64, ch_mult=(1, 2, 2, 2), attn=(1,), num_res_blocks=2)
+ARCH_CH96 = _G(ch=96, ch_mult=(1, 2, 3, 4), attn=(2,), num_res_blocks=2)
+ARCH_BLK128 = _G(ch=128, ch_mult=(1, 1, 1), attn=(2,), num_res_blocks=1)
+ARCH_BLK256 = _G(ch=128, ch_mult=(1, 2, 2), attn=(2,), num_res_blocks=1)
+ARCH_FLASH2 = _G(ch=64, ch_mult=(1, 2), attn=(0,), num_res_blocks=1)
+ARCH_FLASH8 = _G(ch=128, ch_mult=(1, 2), attn=(1,), num_res_blocks=1, img_size=64)
+ARCH_CS384 = _G(ch=128, ch_mult=(1, 3), attn=(1,), num_res_blocks=1)
+ARCH_CS512 = _G(ch=128, ch_mult=(1, 4), attn=(1,), num_res_blocks=1)
+ARCH_A16 = dataclasses.replace(ARCH_A, img_size=16)
+ARCH_A8 = dataclasses.replace(ARCH_A, img_size=8)
+_ALL = lambda n: tuple(range(n))
+_SEAMS37 = (0, 15, 16, 31, 32, 36)
+GEOMETRY_CASES = [
+    # bf16 conv_igemm with Cin = 32 / 96 (a 64-wide K chunk straddles two taps), GroupNorm groups of 1 / 2 / 3
+    Case("tiny-bf16-n5", ARCH_TINY, "bf16", 5, (), _ALL(5)),
+    # ConvTranspose2d by zero insertion on conv_igemm, the guided tail at C = 32 (2n = 6). (ARCH_TINY_CFG upsamples
+    # at now = 64 and takes the sub-pixel form: ch_mult (1, 3) makes now = 96, 96 % 64 != 0)
+    Case("cfg96-bf16-2n6-step", ARCH_CFG96, "bf16", 3, (), _ALL(6), True),
+    # ... and the plain tail kernels' x0 epilogue (tail2_kernel<T, true>), bf16 and fp32
+    Case("tinycfg-bf16-2n6-step-io_mfma0", ARCH_TINY_CFG, "bf16", 3, (("io_mfma", 0),), _ALL(6), True),
+    Case("tinycfg-fp32-2n6-step", ARCH_TINY_CFG, "fp32", 3, (), _ALL(6), True),
+    # Cout = 64 part tiles, two-source gn_apply_kernel, unfused attention S = 256 / C = 128 with vt, concat Cin 192
+    Case("ch64-n5", ARCH_CH64, "bf16", 5, (), _ALL(5)),
+    # ... and at 512 query blocks attn_mfma_kernel<64> (n * S / 64 >= 512)
+    Case("ch64-n128", ARCH_CH64, "bf16", 128, (), (0, 63, 64, 127)),
+    # Cin / Cout 96, 288 (conv_igemm, straddling chunks), Cout 192, attn_kernel<bf16> at S = 64, groups of 3 / 9 / 21
+    Case("ch96-n5", ARCH_CH96, "bf16", 5, (), _ALL(5)),
+    Case("ch96-fp32-n3", ARCH_CH96, "fp32", 3, (), _ALL(3)),
+    Case("blk128-n5", ARCH_BLK128, "bf16", 5, (), _ALL(5)),
+    Case("blk256-n5", ARCH_BLK256, "bf16", 5, (), _ALL(5)),
+    Case("flash2-n2", ARCH_FLASH2, "bf16", 2, (), _ALL(2)),
+    Case("flash8-64px-n2", ARCH_FLASH8, "bf16", 2, (), _ALL(2)),
+    # the channel-split attention where the flash kernel runs by default, one and two query groups a block
+    Case("flash8-64px-n2-attn_wide2", ARCH_FLASH8, "bf16", 2, (("attn_wide", 2),), _ALL(2)),
+    Case("flash8-64px-n2-attn_wide2-nq2", ARCH_FLASH8, "bf16", 2, (("attn_wide", 2), ("attn_wide_nq", 2)), _ALL(2)),
+    Case("cs384-n2-nq2", ARCH_CS384, "bf16", 2, (("attn_wide_nq", 2),), _ALL(2)),
+    Case("cs512-n2-nq2", ARCH_CS512, "bf16", 2, (("attn_wide_nq", 2),), _ALL(2)),
+    # the DDPM model at 4x4 / 2x2 (16 px) and down to 1x1 (8 px): sub-pixel upsample from 2x2 and 1x1, the stride-2
+    # conv 2x2 -> 1x1 with its pruned taps, the one-token AttnBlock fold, the plain bf16 head and tail2_kernel<bf16_t>
+    Case("A-16px-n37", ARCH_A16, "bf16", 37, (), _SEAMS37),
+    Case("A-8px-n37", ARCH_A8, "bf16", 37, (), _SEAMS37),
+]
+CASES += GEOMETRY_CASES
 
 
 def _rb(x):
@@ -631,6 +688,7 @@ class Walker:
         sd = self.sd64
         a, b, _ = self.gn_ab([o["src1"]], "tail.0")
         bias = sd["tail.2.bias"][None, :, None, None]
+        self.note_groups("tail gn_coef" if o["has_coef"] else "tail gn_apply", self.cache["info", o["src1"]]["C"])
         if o["has_coef"]:  # tail_mfma_kernel: GroupNorm + SiLU applied while staging, from the coef buffer
             self.check_gncoef(op, o, coef_key=op, prefix="tail.0")
             self.checked.add(self.kern_tail_gn)
@@ -695,6 +753,9 @@ class Walker:
         self.checked = {(_norm(k), prec) for k in self.checked}
         if self.step:
             self.flags |= {"step pass", "uncond half (label 0)", "guided tail"}
+            # (the census is a forward and names the tail's eps form; the step's launcher runs the <.., true>
+            # instantiation of the same kernel, step_mode 2: pinned by this flag, per kernel and precision)
+            self.flags.add("x0 epilogue (%s, %s)" % (_norm(self.kern[self.nops + 1]), prec))
 
     def note(self, o):
         """What op_info said of a launch that was compared: the coverage pin's second leg."""
@@ -725,10 +786,43 @@ class Walker:
             if (plain and self.sd64[o["name"] + ".weight"].shape[-1] > o["ksize"]) or \
                     (o["tag"] == rt.TAG_CONVT and o["ksize"] == 1):
                 f.add("dead taps pruned")
+                if not self.a.cfg:
+                    f.add("dead taps pruned (DDPM)")
+            # the shape classes the kernel names cannot tell apart
+            srcs = [self.cache["info", i] for i in (o["src1"], o["src2"]) if i >= 0]
+            Cin, kern = sum(ai["C"] for ai in srcs), o["kernel"]
+            if self.bf and Cin % 64:
+                f.add("bf16 Cin %% 64 != 0 (%s)" % kern)
+            if o["Cout"] % 128:
+                f.add("Cout %% 128 != 0 (%s)" % kern)
+            if o["zins"]:
+                f.add("zins (%s)" % kern)
+            if o["subpix"] == 1 and srcs[0]["H"] * srcs[0]["W"] in (1, 4):
+                f.add("subpix 1 from HW %d" % (srcs[0]["H"] * srcs[0]["W"]))
+            if o["tag"] == rt.TAG_ATTN_S1 and not self.a.cfg:
+                f.add("tag 3 (DDPM)")
+            # images a pixel tile of the launch holds (conv_small: 64 pixels; the others: 128; the sub-pixel forms
+            # tile the input grid)
+            g = srcs[0] if o["subpix"] else self.cache["info", o["dst"]]
+            per = (64 if kern == "SMALL" else 128) // (g["H"] * g["W"])
+            if min(per, self.nb) > 16:
+                f.add("tile of more than 16 images (%s)" % kern)
+        elif o["kind"] == "gncoef":
+            self.note_groups("gn_coef", sum(self.cache["info", i]["C"] for i in (o["src1"], o["src2"]) if i >= 0))
         elif o["kind"] == "gn":
             f.add("gn silu %d" % o["silu"])
+            self.note_groups("gn_apply", sum(self.cache["info", i]["C"] for i in (o["src1"], o["src2"]) if i >= 0))
+            if o["src2"] >= 0:
+                f.add("gn_apply over two sources")
         elif o["kind"] == "attn":
             f.add("attn vt" if o["vt"] >= 0 else "attn v from qkv")
+
+    def note_groups(self, who, C):
+        gs = C // 32
+        if gs < 8:
+            self.flags.add("%s group size < 8" % who)
+        if 8 % gs:
+            self.flags.add("%s group size not dividing 8" % who)
 
     def worst(self):
         """Per check class, the worst ratio (error / bound, or rel-L2 / (factor x emulation))."""
@@ -786,21 +880,57 @@ UNREACHED = {
 }
 
 
+# The attention, AttnBlock, head and tail kernels by instantiation: every one the launch sites of kernels.hip /
+# conv.hip can emit in the shipped build (launch_attn_block, launch_attn, launch_head / _head_mfma, launch_tail /
+# _tail_mfma), as the census spells it, with the precisions it serves. A family name would be satisfied by one
+# instantiation of a template for all of them.
+_BF, _BOTH = ("bf16",), ("bf16", "fp32")
+EXPECTED_INSTANCES = {
+    "attn_block_kernel<128>": _BF, "attn_block_kernel<256>": _BF, "attn_block_kernel<384>": _BF,
+    "attn_block_split_kernel<384, 2>": _BF, "attn_block_split_kernel<384, 4>": _BF,
+    "attn_block_split_kernel<384, 6>": _BF,
+    "attn_mfma_kernel<32>": _BF, "attn_mfma_kernel<64>": _BF,
+    "attn_flash_kernel<2>": _BF, "attn_flash_kernel<4>": _BF, "attn_flash_kernel<8>": _BF,
+    "attn_cs_kernel<1024, 1, 8>": _BF, "attn_cs_kernel<512, 1>": _BF, "attn_cs_kernel<512, 2>": _BF,
+    "attn_cs_kernel<384, 1>": _BF, "attn_cs_kernel<384, 2>": _BF, "attn_cs_kernel<256, 1>": _BF,
+    "attn_cs_kernel<256, 2>": _BF,
+    "attn_kernel<T>": _BOTH,
+    "head_mfma_kernel": _BF, "head_kernel<T>": _BOTH,
+    # (each tail kernel's <.., true> instantiation, the x0 epilogue of the sampler step, is launched by the same
+    # launcher under step_mode 2; the census is a forward and never names it: REQUIRED_FLAGS "x0 epilogue (..)")
+    "tail_mfma_kernel<128, 512>": _BF, "tail2_kernel<T>": _BOTH, "tail_kernel<T>": _BOTH,
+}
+UNREACHED.update({
+    ("tail_kernel<T>", "bf16"): "the per-pixel tail: image rows wider than 64 pixels (or 64 % W != 0) only, i.e. 128 px "
+                                "and up, where the bf16 MFMA tail is eligible too, so io_mfma 0 besides; the per-op "
+                                "walk holds every activation of a forward in float64 on the host and has no case at "
+                                "those sizes (the 256 px forward is held whole in test_gpu_parity.py)",
+    ("tail_kernel<T>", "fp32"): "as above: fp32 at 128 px and up",
+    "x0 epilogue (tail_kernel<T>, bf16 | fp32)": "tail_kernel<T, true>: as above, in the sampler step's x0 pass",
+})
+
 # the same forms by what op_info says of the compared launches, which the names cannot tell apart: the ConvKernel
 # enumerator per precision (conv_pipe<T, 2, true> is PIPE_LIN and PIPE_SUBPIX, bf16 and fp32) ...
 REQUIRED_FORMS = [(k, "bf16") for k in rt.CONV_KERNELS if k != "PIPE"] + [("PIPE_LIN", "fp32"), ("PIPE_SUBPIX", "fp32")]
-# ... the kernels that serve both precisions, and the create-time alternatives' bf16 forms (io_mfma 0, attn_fuse 0) ...
-REQUIRED_NAMES = [("gn_apply_kernel<T>", "bf16"), ("gn_apply_kernel<T>", "fp32"), ("attn_kernel<T>", "bf16"),
-                  ("attn_kernel<T>", "fp32"), ("head_kernel<T>", "bf16"), ("head_kernel<T>", "fp32"),
-                  ("head_mfma_kernel", "bf16"), ("tail_mfma_kernel", "bf16"),
-                  (("tail2_kernel", "tail_kernel<"), "bf16"), (("tail2_kernel", "tail_kernel<"), "fp32"),
-                  ("attn_mfma_kernel", "bf16"), ("conv_pipe<T,2,true>", "bf16"), ("conv_pipe<T,2,true>", "fp32")]
-# ... and the folds and passes the cases exist for (Walker.note)
+# ... the kernels that serve both precisions ...
+REQUIRED_NAMES = [("gn_apply_kernel<T>", "bf16"), ("gn_apply_kernel<T>", "fp32"),
+                  ("conv_pipe<T, 2, true>", "bf16"), ("conv_pipe<T, 2, true>", "fp32")]
+# ... and the folds, passes and shape classes the cases exist for (Walker.note)
 REQUIRED_FLAGS = ["gn_fold", "gn_out", "sc_split", "splitk_epilogue_kernel", "fused GroupNorm input",
                   "coef from gn_coef_kernel", "vt", "subpix 1", "subpix 2", "ksplit 3", "resid", "temb", "temb + cemb",
                   "tag 1", "tag 2", "tag 3", "tag 4", "dead taps pruned", "gn silu 0", "gn silu 1", "attn vt",
                   "attn v from qkv", "kS > 1 (SMALL)", "kS > 1 (PIPE_LIN)", "kS > 1 (PIPE_SUBPIX)", "step pass",
-                  "uncond half (label 0)", "guided tail"]
+                  "uncond half (label 0)", "guided tail",
+                  # geometries outside the shipped configurations
+                  "bf16 Cin % 64 != 0 (IGEMM)", "Cout % 128 != 0 (SMALL)", "Cout % 128 != 0 (PIPE_LIN)",
+                  "Cout % 128 != 0 (PIPE_SUBPIX)", "Cout % 128 != 0 (IGEMM)", "zins (IGEMM)",
+                  "gn_apply group size < 8", "gn_apply group size not dividing 8", "gn_coef group size < 8",
+                  "gn_coef group size not dividing 8", "tail gn_coef group size < 8",
+                  "tail gn_coef group size not dividing 8", "tail gn_apply group size < 8", "gn_apply over two sources",
+                  "subpix 1 from HW 1", "subpix 1 from HW 4", "tag 3 (DDPM)", "dead taps pruned (DDPM)",
+                  "tile of more than 16 images (SMALL)", "tile of more than 16 images (PIPE_SUBPIX)",
+                  "x0 epilogue (tail_mfma_kernel<128,512>, bf16)", "x0 epilogue (tail2_kernel<T>, bf16)",
+                  "x0 epilogue (tail2_kernel<T>, fp32)"]
 UNREACHED.update({
     "conv1x1_stream_kernel<128|256|384|512|640, 7>": "the 7-stage ring: option conv1x1 = 2 exists in diagnostic builds "
                                                      "only; the shipped library refuses it (itsd_set_option)",
@@ -809,10 +939,10 @@ UNREACHED.update({
 
 
 def test_every_kernel_form_was_checked():
-    """The hand-written lists against what the cases compared: every kernel-name form (census), every ConvKernel
-    enumerator per precision and every fold (op_info) at least once. The attention, AttnBlock, head and tail kernels
-    are listed by the names the census reports for them. splitk_epilogue_kernel is a conv's second launch, which the
-    census never names: it is pinned by op_info's epilogue flag."""
+    """The hand-written lists against what the cases compared: every kernel name (census) by exact instantiation and,
+    where one name serves both, per precision; every ConvKernel enumerator per precision; every fold and shape class
+    (op_info / act_info) at least once. splitk_epilogue_kernel is a conv's second launch, which the census never
+    names: it is pinned by op_info's epilogue flag."""
     seen, forms, flags = set(), set(), set()
     for c in CASES:
         w = _walked(c.id)
@@ -823,20 +953,20 @@ def test_every_kernel_form_was_checked():
     print("kernels checked:", sorted(seen))
     print("conv forms checked:", sorted(forms))
     print("folds checked:", sorted(flags))
+    assert all(reason for reason in UNREACHED.values())
     missing = [k for k in EXPECTED_KERNELS if _norm(k) not in names and k not in UNREACHED]
-    # (the fp32 tail is tail2_kernel or tail_kernel by shape: one family)
-    families = (("attn_mfma_kernel",), ("attn_flash_kernel",), ("attn_cs_kernel",), ("attn_block_kernel",),
-                ("attn_block_split_kernel",), ("attn_kernel",), ("head_mfma_kernel",), ("head_kernel",),
-                ("tail_mfma_kernel",), ("tail2_kernel", "tail_kernel"))
-    missing += [fam for fam in families if not any(f in k for f in fam for k in names)]
+    missing += [(k, p) for k, precs in EXPECTED_INSTANCES.items() for p in precs
+                if (_norm(k), p) not in seen and (k, p) not in UNREACHED]
     missing += [f for f in REQUIRED_FORMS if f not in forms]
-    alts = lambda n: n if isinstance(n, tuple) else (n,)
-    missing += [(n, p) for n, p in REQUIRED_NAMES if not any(a in k and p == q for a in alts(n) for k, q in seen)]
+    missing += [(n, p) for n, p in REQUIRED_NAMES if (_norm(n), p) not in seen]
     missing += [f for f in REQUIRED_FLAGS if f not in flags]
     assert not missing, f"no case compared {missing}"
-    listed = {_norm(k) for k in EXPECTED_KERNELS}
-    extra = [k for k in names if k not in listed and not any(f in k for fam in families for f in fam)]
+    listed = {_norm(k) for k in EXPECTED_KERNELS} | {_norm(k) for k in EXPECTED_INSTANCES}
+    extra = [k for k in names if k not in listed]
     assert not extra, f"the census names kernels this list does not know: {extra}"
+    stale = [k for k in UNREACHED if (k in EXPECTED_KERNELS and _norm(k) in names) or
+             (isinstance(k, tuple) and (_norm(k[0]), k[1]) in seen)]
+    assert not stale, f"listed as unreached, yet compared: {stale}"
 
 
 @pytest.mark.parametrize("arch,n", [(ARCH_A, 5), (ARCH_C, 4)], ids=["A-n5", "C-n4"])
