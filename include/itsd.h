@@ -239,7 +239,9 @@ enum { ITSD_TAG_NONE = 0,
        ITSD_TAG_DOWN_MERGE = 2,  /* CFG DownSample `name`: c1 (3x3) + c2 (5x5) as one 5x5 conv */
        ITSD_TAG_ATTN_S1 = 3,     /* one-token AttnBlock `name`: resid + proj(proj_v(src1)), src1 = its GroupNorm */
        ITSD_TAG_CONVT = 4,       /* ConvTranspose2d(5, 2, 2, 1) `name` */
-       ITSD_TAG_ATTNBLOCK = 5 }; /* the fused AttnBlock `name` (GroupNorm, q|k|v, attention, proj, + x) */
+       ITSD_TAG_ATTNBLOCK = 5 }; /* the fused AttnBlock `name` (GroupNorm, q|k|v, attention, proj, + x), run with
+                                    proj_q^T proj_k and proj proj_v folded at create: bf16 roundings of the GroupNorm
+                                    output, the two folded projections, the softmax weights and the output */
 #define ITSD_ACT_PROJ (-2)
 typedef struct {
   int32_t kind;                    /* ITSD_OP_* */

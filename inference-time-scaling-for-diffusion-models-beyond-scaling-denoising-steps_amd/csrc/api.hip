@@ -132,7 +132,7 @@ struct Op {
   int S = 0, C = 0;
   int vt = -1, vt_from = 0;  // channel-major V buffer (conv: couts >= vt_from go there; attn: reads it)
   size_t coef = SIZE_MAX;    // GNCOEF: output; CONV: GroupNorm+SiLU coefficients of the input (fused conv)
-  size_t wt2 = 0, bias2 = 0;  // ATTNBLOCK: the proj matrix (fragment-packed) and bias; wt / bias: q|k|v
+  size_t bias2 = 0;  // ATTNBLOCK: the proj bias bp; wt / bias: the folded [M | W'] rows (fragment-packed) and [u | b']
   size_t gn_gamma = SIZE_MAX, gn_beta = SIZE_MAX;  // CONV with coef: its input GroupNorm's affine (gn_fold)
   // a ResBlock's block2 conv and its 1x1 shortcut (conv3x3_gn_p5_kernel folds the shortcut in as K slices, ConvArgs
   // sc_*): on block2, the shortcut op, its weights in fragment order and the two biases summed; on the shortcut, block2
@@ -216,7 +216,7 @@ struct itsd_unet {
   void* zero_page = nullptr;  // 256 KiB of zeros (conv DMA source for padding, conv.hip zero_of_block)
   float* splitk_ws = nullptr;  // split-K partial tiles (shared by all convs: they run in stream order)
   int* tickets = nullptr;      // in-launch split-K counters (conv3x3_gn_p5_kernel), zero between launches
-  int* attn_sync = nullptr;    // attn_block_split_kernel's per-image hand-off counters [nb_max][2] (monotonic)
+  int* attn_sync = nullptr;    // attn_block_split_kernel's per-image hand-off counter [nb_max] (monotonic)
   static constexpr long long kSplitkCap = 16ll << 20;  // floats (64 MB)
 
   hipStream_t stream = nullptr;
@@ -592,27 +592,58 @@ struct Builder {
       }
     }
     if (attn && u->bf16 && itsd::g_attn_fuse && attn_block_ok(H * W, out_ch)) {
-      // the whole AttnBlock in one launch (kernels.hip attn_block_kernel)
+      // the whole AttnBlock in one launch (kernels.hip attn_block_kernel). The block is linear on either side of
+      // the softmax and its weights are constants, so the four projections fold into two (fp64 here from the fp32
+      // weights as loaded, one bf16 rounding in pack_frag):
+      //   scores  (h Wq^T + bq)(h Wk^T + bk)^T = (h M + u) h^T + [terms constant along the key axis, which the
+      //           softmax over keys cancels exactly],  M = Wq^T Wk, u = Wk^T bq (bk never reaches the output);
+      //   output  proj(P v) = P (h W' + b') + bp,  W' = (Wp Wv)^T, b' = Wp bv.
+      // As 1x1-conv matrices [Cout][Cin]: Wm[j][i] = sum_a Wk[a][j] Wq[a][i], Wf[o][i] = sum_c Wp[o][c] Wv[c][i].
       const std::string a = p + ".attn";
-      const int64_t cc = (int64_t)out_ch * out_ch;
-      std::vector<float> wcat((size_t)3 * cc, 0.f);
+      const int C = out_ch;
+      const int64_t cc = (int64_t)C * C;
       const float* wq = get(a + ".proj_q.weight", cc);
       const float* wk = get(a + ".proj_k.weight", cc);
       const float* wv = get(a + ".proj_v.weight", cc);
-      if (wq && wk && wv) {
-        std::memcpy(wcat.data(), wq, cc * 4);
-        std::memcpy(wcat.data() + cc, wk, cc * 4);
-        std::memcpy(wcat.data() + 2 * cc, wv, cc * 4);
+      const float* wp = get(a + ".proj.weight", cc);
+      const float* bq = get(a + ".proj_q.bias", C);
+      const float* bv = get(a + ".proj_v.bias", C);
+      get(a + ".proj_k.bias", C);  // (validated and counted as the reference's key, never read)
+      std::vector<float> wcat((size_t)2 * cc, 0.f), bcat((size_t)2 * C, 0.f);
+      if (wq && wk && wv && wp && bq && bv) {
+        std::vector<double> acc((size_t)cc);
+        // fold(A, B, ta): acc[r][i] = sum_a (ta ? A[a][r] : A[r][a]) B[a][i]
+        auto fold = [&](const float* A, const float* B, bool ta, float* dst) {
+          std::fill(acc.begin(), acc.end(), 0.0);
+          for (int r = 0; r < C; ++r) {
+            double* row = acc.data() + (size_t)r * C;
+            for (int k = 0; k < C; ++k) {
+              const double w = (double)(ta ? A[(size_t)k * C + r] : A[(size_t)r * C + k]);
+              const float* br = B + (size_t)k * C;
+              for (int i = 0; i < C; ++i) row[i] += w * (double)br[i];
+            }
+          }
+          for (int64_t i = 0; i < cc; ++i) dst[i] = (float)acc[i];
+        };
+        fold(wk, wq, true, wcat.data());        // M rows: Wk^T Wq
+        fold(wp, wv, false, wcat.data() + cc);  // W' rows: Wp Wv
+        for (int j = 0; j < C; ++j) {
+          double su = 0.0, sb = 0.0;
+          for (int k = 0; k < C; ++k) {
+            su += (double)wk[(size_t)k * C + j] * (double)bq[k];
+            sb += (double)wp[(size_t)j * C + k] * (double)bv[k];
+          }
+          bcat[j] = (float)su;
+          bcat[C + j] = (float)sb;
+        }
       }
       Op ab;
       ab.kind = OP_ATTNBLOCK;
       ab.src1 = o;
       ab.gamma = f32(a + ".group_norm.weight", out_ch);
       ab.beta = f32(a + ".group_norm.bias", out_ch);
-      ab.wt = pack_frag(wcat.data(), 3 * out_ch, out_ch, 1);
-      ab.bias = concat_f32({get(a + ".proj_q.bias", out_ch), get(a + ".proj_k.bias", out_ch),
-                            get(a + ".proj_v.bias", out_ch)}, out_ch);
-      ab.wt2 = pack_frag(get(a + ".proj.weight", cc), out_ch, out_ch, 1);
+      ab.wt = pack_frag(wcat.data(), 2 * out_ch, out_ch, 1);  // [M rows | W' rows]
+      ab.bias = ar.add(bcat.data(), bcat.size() * 4);          // [u | b']
       ab.bias2 = f32(a + ".proj.bias", out_ch);
       ab.S = H * W;
       ab.C = out_ch;
@@ -1113,22 +1144,19 @@ int launch_op(itsd_unet* u, const Op& o, const RunCtx& c, const ConvLaunch* cl, 
     a.spi = stat_spi(in.H * in.W, in.spi);
     a.gamma = u->wp(o.gamma);
     a.beta = u->wp(o.beta);
-    a.wqkv = (const bf16_t*)(u->wdev + o.wt);
-    a.bqkv = u->wp(o.bias);
-    a.wp = (const bf16_t*)(u->wdev + o.wt2);
+    a.wmv = (const bf16_t*)(u->wdev + o.wt);
+    a.buv = u->wp(o.bias);
     a.bp = u->wp(o.bias2);
     a.out = (bf16_t*)u->ap(o.dst);
     a.out_stats = out.stats != SIZE_MAX ? (float*)(u->ws + out.stats) : nullptr;
     a.scale = (float)std::pow((double)o.C, -0.5);
     a.n = c.nb;
     a.S = o.S;
-    // attn_block_split_kernel's slabs in the split-K workspace (ops run in stream order; <= 4 MB of
-    // partial scores at n * G <= 256, then the O slab)
-    if ((long long)c.nb * 64 * o.C * 2 / 4 + (4ll << 20) / 4 <= itsd_unet::kSplitkCap) {
-      a.spart = u->splitk_ws;
-      a.oslab = (bf16_t*)(u->splitk_ws + (4ll << 20) / 4);
-      a.sync = u->attn_sync;
-    }
+    // attn_block_split_kernel's partial-score slab in the split-K workspace (ops run in stream order; <= 4 MB
+    // at n * G <= 256)
+    static_assert((4ll << 20) / 4 <= itsd_unet::kSplitkCap, "the partial-score slab fits the split-K workspace");
+    a.spart = u->splitk_ws;
+    a.sync = u->attn_sync;
     a.err = u->d_nan + 1;
     a.spin_bound = itsd::g_spin_bound;
     e = launch_attn_block(a, o.C, s);
@@ -1153,7 +1181,8 @@ double op_flops(const itsd_unet* u, const Op& o, int nb) {
     return 2.0 * nb * out.H * out.W * (double)o.Cout * (o.subpix == 1 ? o.K * 4 / 9 : o.K);
   }
   if (o.kind == OP_ATTN) return 2.0 * 2.0 * nb * (double)o.S * o.S * o.C;
-  if (o.kind == OP_ATTNBLOCK)  // q|k|v and proj projections + the two attention products
+  if (o.kind == OP_ATTNBLOCK)  // the algorithmic count: q|k|v and proj projections + the two attention products (the
+    // folded kernel executes two C x C projections, not four: 2 S (2 C^2) + 2 * 2 S^2 C an image)
     return 2.0 * nb * (double)o.S * (4.0 * o.C * o.C) + 2.0 * 2.0 * nb * (double)o.S * o.S * o.C;
   return 0.0;
 }
@@ -1601,8 +1630,8 @@ int itsd_unet_create(const itsd_unet_desc* desc, const itsd_tensor_view* weights
   HIPCHK(hipMalloc(&u->splitk_ws, itsd_unet::kSplitkCap * 4));
   HIPCHK(hipMalloc(&u->tickets, itsd::kTicketCap * 4));
   HIPCHK(hipMemset(u->tickets, 0, itsd::kTicketCap * 4));
-  HIPCHK(hipMalloc(&u->attn_sync, (size_t)u->nb_max * 2 * 4));
-  HIPCHK(hipMemset(u->attn_sync, 0, (size_t)u->nb_max * 2 * 4));
+  HIPCHK(hipMalloc(&u->attn_sync, (size_t)u->nb_max * 4));
+  HIPCHK(hipMemset(u->attn_sync, 0, (size_t)u->nb_max * 4));
   HIPCHK(hipMalloc(&u->proj_buf, (size_t)d.max_batch * u->sumC * 4));
   CHK(alloc_rows(u.get(), std::max(d.max_batch, d.num_labels + 1)));
   if (u->cfg) {

@@ -272,20 +272,18 @@ struct AttnBlockArgs {
   const float* st;        // its GroupNorm statistics slab [n * spi][2][C]
   int spi;                // statistics slots per image
   const float* gamma; const float* beta;
-  const bf16_t* wqkv;     // [3C/32][C/16][64][8]: q rows, k rows, v rows
-  const float* bqkv;      // [3C]
-  const bf16_t* wp;       // [C/32][C/16][64][8]
-  const float* bp;        // [C]
+  const bf16_t* wmv;      // [2C/32][C/16][64][8]: the folded M = Wq^T Wk rows, then the W' = (Wp Wv)^T rows
+  const float* buv;       // [2C]: u = Wk^T bq | b' = Wp bv
+  const float* bp;        // [C] the proj bias
   bf16_t* out;            // [n][S][C]
   float* out_stats;       // [n][2][C] (one slot per image) or null
   float scale;            // C^-0.5
   int n;
   int S;                  // tokens an image: 64 (one image a block) or 16 (4 images a block)
-  // attn_block_split_kernel (an image's work over G blocks, small batches): partial-score and O slabs
-  // (write-through hand-offs) and two monotonic counters per image
+  // attn_block_split_kernel (an image's work over G blocks, small batches): the partial-score slab
+  // (write-through hand-off) and one monotonic counter per image
   float* spart;           // [n][G][4 tiles][64 lanes][16] fp32
-  bf16_t* oslab;          // [n][64][C] bf16
-  int* sync;              // [n][2], never reset (targets from each block's own add)
+  int* sync;              // [n], never reset (targets from each block's own add)
   int* err;               // device status word: bit 0 set when a hand-off wait exhausted its poll bound
   int spin_bound;         // polls before a hand-off wait gives up (itsd_set_option "spin_bound", diagnostic)
 };

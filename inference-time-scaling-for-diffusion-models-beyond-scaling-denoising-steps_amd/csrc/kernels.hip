@@ -318,22 +318,28 @@ __global__ __launch_bounds__(256) void attn_mfma_kernel(AttnArgs a) {
 // attn_block_kernel<C>: one image's whole AttnBlock (Model.py:145-164) per block -- Arch A's 8x8
 // level (S = 64 tokens, C = 384), where the unfused path ran a materialised GroupNorm, the q|k|v
 // 1x1 conv (C x 3C over 64 tokens), the attention kernel and the proj conv as four launches with
-// three HBM round trips, 2 % of MFMA peak in the attention itself. Here:
+// three HBM round trips, 2 % of MFMA peak in the attention itself.
+// The block is linear on either side of the softmax, so the Builder folds its four C x C projections into
+// two (api.hip, the OP_ATTNBLOCK branch): with M = Wq^T Wk, u = Wk^T bq, W' = (Wp Wv)^T, b' = Wp bv
+//     out = x + softmax((hn M + u) hn^T / sqrt(C)) (hn W' + b') + bp
+// (the score terms that are constant along the key axis cancel in the softmax). Here:
 //   0. GroupNorm(32, C) of x: group mean / rstd in fp64 from the producer's statistics slab, x
 //      staged as hn = bf16(x a + b) in LDS ([token][C], 16-B chunks XOR-swizzled by token & 15);
-//   1. V^T = (hn Wv^T + bv)^T -> LDS [C][64] (D[token][c] with Wv fragments as the B operand, so a
-//      lane holds 4 consecutive tokens of one channel: 8-B channel-major stores);
-//   2. per 128-channel chunk: Q_c, K_c = hn W^T + b (D[c][token]: weights as A) -> LDS [64][128],
-//      and the scores S^T[key][query] += K_c Q_c^T accumulate in registers (one 32x32 tile a wave);
-//   3. softmax over keys in fp32 (S^T staged through LDS, 4 lanes a query), P [query][key] bf16;
-//   4. O^T = V^T P^T (both operands from LDS) -> O [token][C] bf16 in LDS (hn's space);
-//   5. out = x + O Wp^T + bp, one bf16 rounding, 16-B stores (permlane32 swap), and the consumer
-//      GroupNorm statistics of out (one slot per image) by lane butterflies.
-// Roundings as the unfused path: hn, q / k / v, P and O in bf16, fp32 accumulation.
-// 8 waves (512 threads, __launch_bounds__(512, 1)): the weight-streaming phases give each wave whole
-// 32-channel blocks (V / proj: blocks w, w + 8; q|k: Q on waves 0-3, K on 4-7), the score / softmax / PV
-// phases split queries and channel blocks over the waves; weights (fragment-packed [Cout/32][K/16][64][8]
-// bf16) stream from L2 into VGPRs with an 8-k-step prefetch; one block per image.
+//   1. ONE weight-streaming phase over the 2 C / 32 fragment rows [M | W'], 2 C / 256 whole 32-channel
+//      blocks a wave (row w + 8 b) over both token blocks, so every fragment is streamed once per block:
+//      T = hn M + u -> LDS [token][C] (D[c][token]: weights as A), V'^T = (hn W' + b')^T -> LDS [C][64]
+//      (D[token][c], weights as B: a lane holds 4 consecutive tokens of one channel, 8-B channel-major stores);
+//   2. the scores S^T[key][query] = hn T^T over all C channels, one 32x32 tile a wave (waves 0-3), both
+//      operands from LDS;
+//   3. softmax over keys in fp32 (S^T staged through LDS, 8 lanes a query), P [query][key] bf16;
+//   4. O^T = V'^T P^T (both operands from LDS), D[c][query] in registers;
+//   5. out = x + O + bp from those registers, one bf16 rounding, 16-B stores (permlane32 swap), and the
+//      consumer GroupNorm statistics of out (one slot per image) by lane butterflies.
+// Roundings: hn, T, V', P in bf16 and the output's one; fp32 accumulation. Bytes streamed per block: 4 C^2
+// (590 KB at C = 384; the four-projection form streamed 8 C^2).
+// 8 waves (512 threads, __launch_bounds__(512, 1)); weights (fragment-packed [Cout/32][K/16][64][8] bf16)
+// stream from L2 into VGPRs with an 8-k-step prefetch whose first fragments are issued behind the x loads;
+// one block per image.
 
 #ifdef ITSD_STAMPS
 // Diagnostic build only: attn_block_kernel's phase timeline (s_memrealtime), [block % 1024][wave][slot]
@@ -349,6 +355,74 @@ __device__ __forceinline__ void atl(int slot) {
 #define ATL(slot)
 #endif
 
+// The AttnBlock's epilogue for one tile of O^T accumulators (D[c][token]: lane (rl, hh) holds token tk and
+// channels c0 + 8 g + 4 hh + e): out = x + O + bp, one bf16 rounding, 16-B stores (permlane32 swap), and, with
+// sp, the tile's 32 tokens' sums of the rounded outputs and their squares by lane butterflies ->
+// sp[(0 sums | 1 squares) * sps + channel - c0]. x / out: the image's [64][C]. bad: every output NaN (a failed hand-off).
+__device__ __forceinline__ void attn_out_tile(const f32x16& acc, const bf16_t* x, bf16_t* out, const float* bp, int C,
+                                              int tk, int c0, int rl, int hh, bool bad, float* sp, int sps) {
+  float v[32];
+  uint32_t wv[4][2];
+  const float nan = __builtin_nanf("");
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    const int c = c0 + 8 * g + 4 * hh;
+    const f32x4 bb = *(const f32x4*)(bp + c);
+    const uint2 rr = *(const uint2*)(x + (size_t)tk * C + c);
+    const float v0 = bad ? nan : acc[4 * g + 0] + bb[0] + __uint_as_float(rr.x << 16);
+    const float v1 = bad ? nan : acc[4 * g + 1] + bb[1] + __uint_as_float(rr.x & 0xffff0000u);
+    const float v2 = bad ? nan : acc[4 * g + 2] + bb[2] + __uint_as_float(rr.y << 16);
+    const float v3 = bad ? nan : acc[4 * g + 3] + bb[3] + __uint_as_float(rr.y & 0xffff0000u);
+    wv[g][0] = pk_bf16(v0, v1);
+    wv[g][1] = pk_bf16(v2, v3);
+    const float r0 = __uint_as_float(wv[g][0] << 16), r1 = __uint_as_float(wv[g][0] & 0xffff0000u);
+    const float r2 = __uint_as_float(wv[g][1] << 16), r3 = __uint_as_float(wv[g][1] & 0xffff0000u);
+    v[4 * g + 0] = r0; v[16 + 4 * g + 0] = r0 * r0;
+    v[4 * g + 1] = r1; v[16 + 4 * g + 1] = r1 * r1;
+    v[4 * g + 2] = r2; v[16 + 4 * g + 2] = r2 * r2;
+    v[4 * g + 3] = r3; v[16 + 4 * g + 3] = r3 * r3;
+  }
+#pragma unroll
+  for (int gp = 0; gp < 4; gp += 2) {
+    u32x4 o;
+#pragma unroll
+    for (int d = 0; d < 2; ++d) {
+      const auto sw = __builtin_amdgcn_permlane32_swap(wv[gp][d], wv[gp + 1][d], false, false);
+      o[d] = sw[0];
+      o[2 + d] = sw[1];
+    }
+    *(u32x4*)(out + (size_t)tk * C + c0 + 8 * (gp + hh)) = o;
+  }
+  if (sp) {  // the tile's 32 lanes: butterfly (lanes rl < 16 end with the sums, the others with the squares)
+    auto xchg = [](float xf, auto wc) {
+      constexpr int wd = decltype(wc)::value;
+      const int xi = __builtin_bit_cast(int, xf);
+      int r;
+      if constexpr (wd == 1) r = __builtin_amdgcn_update_dpp(0, xi, 0xB1, 0xF, 0xF, false);
+      else if constexpr (wd == 2) r = __builtin_amdgcn_update_dpp(0, xi, 0x4E, 0xF, 0xF, false);
+      else if constexpr (wd == 8) r = __builtin_amdgcn_update_dpp(0, xi, 0x128, 0xF, 0xF, false);
+      else r = __builtin_amdgcn_ds_swizzle(xi, 0x1F | (wd << 10));
+      return __builtin_bit_cast(float, r);
+    };
+    auto halve = [&](auto wc) {
+      constexpr int wd = decltype(wc)::value;
+      const bool up = (rl & wd) != 0;
+#pragma unroll
+      for (int ii = 0; ii < wd; ++ii) {
+        const float lo = v[ii], hi = v[ii + wd];
+        v[ii] = (up ? hi : lo) + xchg(up ? lo : hi, wc);
+      }
+    };
+    halve(std::integral_constant<int, 16>{});
+    halve(std::integral_constant<int, 8>{});
+    halve(std::integral_constant<int, 4>{});
+    halve(std::integral_constant<int, 2>{});
+    halve(std::integral_constant<int, 1>{});
+    const int e = rl & 15;
+    sp[(rl >> 4) * sps + 8 * (e >> 2) + 4 * hh + (e & 3)] = v[0];
+  }
+}
+
 // (round 4's 4-images-a-block form for the 4x4 middle block, S = 16, measured slower than the unfused ops
 // at N = 32 and equal at N = 256, was removed in round 5)
 #ifndef ITSD_ATTN_PF
@@ -356,13 +430,17 @@ __device__ __forceinline__ void atl(int slot) {
 #endif
 template <int C>
 __global__ __launch_bounds__(512, 1) void attn_block_kernel(AttnBlockArgs a) {
-  constexpr int S = 64, KS = C / 16, CB = C / 32, CBW = CB / 4, NCH = C / 128, PF = ITSD_ATTN_PF;
+  constexpr int S = 64, KS = C / 16, CB = C / 32, CBW = CB / 4, NU = 2 * CB / 8, PF = ITSD_ATTN_PF;
   static_assert(C % 128 == 0, "C");
-  constexpr int R_VT = S * C * 2, R_QK = R_VT + C * 128, R_GS = R_QK + 2 * S * 256, R_ST = R_GS + 32 * 2 * 4;
+  // hn [64][C] | V'^T [C][64] | T [64][C], later the scores S [64][64 + 4] fp32 and P [64][64] | group (mean, rstd) |
+  // the two token blocks' statistics
+  constexpr int SPB = S * (S + 4) * 4 + S * 128;
+  constexpr int R_VT = S * C * 2, R_T = R_VT + C * 128, R_GS = R_T + (S * C * 2 > SPB ? S * C * 2 : SPB), R_ST = R_GS + 32 * 2 * 4;
+  static_assert(R_ST + 2 * C * 2 * 4 <= 160 * 1024, "LDS");
   __shared__ __attribute__((aligned(16))) char sm[R_ST + 2 * C * 2 * 4];
   const int tid = threadIdx.x, lane = tid & 63, rl = lane & 31, hh = lane >> 5;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wq = w & 3, wt = w >> 2;  // wave = (channel-block group, token block)
+  const int wq = w & 3, wt = w >> 2;  // phases 4 / 5: wave = (channel-block group, query block)
   const int img = blockIdx.x;
   ATL(0);
   const bf16_t* x = a.x + (size_t)img * S * C;
@@ -370,8 +448,8 @@ __global__ __launch_bounds__(512, 1) void attn_block_kernel(AttnBlockArgs a) {
   auto rowc = [](int r, int ch, int rowbytes) { return r * rowbytes + ((ch ^ (r & 15)) << 4); };
   // [row][64] bf16 image (128-B rows), chunk ch of row r at ch ^ ((r >> 1) & 7)
   auto row64 = [](int r, int ch) { return r * 128 + ((ch ^ ((r >> 1) & 7)) << 4); };
-  auto frag = [&](const bf16_t* W, int cb, int st) -> const bf16x8* {
-    return (const bf16x8*)((const char*)W + ((size_t)cb * KS + st) * 1024 + lane * 16);
+  auto frag = [&](int row, int st) -> const bf16x8* {
+    return (const bf16x8*)((const char*)a.wmv + ((size_t)row * KS + st) * 1024 + lane * 16);
   };
   // ---- 0. GroupNorm statistics -> (mean, rstd) per group; hn (all x loads issued before any use)
   constexpr int XU = S * (C / 8) / 512;  // 16-B units of x per thread
@@ -381,18 +459,13 @@ __global__ __launch_bounds__(512, 1) void attn_block_kernel(AttnBlockArgs a) {
     const int u = tid + 512 * i, t = u / (C / 8), ch = u - t * (C / 8);
     xv[i] = *(const u32x4*)(x + (size_t)t * C + ch * 8);
   }
-  // (round 5) every weight stream's first PF fragments are issued ahead of its phase: phase 1's here, behind the
-  // x loads (they arrive during the group statistics and hn staging), phase 2's chunk 0 in phase 1's last PF
-  // steps and chunk c + 1 after chunk c's Q / K stores, phase 5's before the softmax -- no phase opens with a
-  // memory round trip
-  constexpr int NBW = (CB + 7) / 8;
-  bf16x8 bw[PF][NBW];
+  // the weight stream's first PF fragments are issued here, behind the x loads (they depend on no earlier kernel
+  // and arrive during the group statistics and hn staging): the phase does not open with a memory round trip
+  bf16x8 bw[PF][NU];
 #pragma unroll
   for (int p = 0; p < PF; ++p)
 #pragma unroll
-    for (int b = 0; b < NBW; ++b)
-      if (w + 8 * b < CB) bw[p][b] = *frag(a.wqkv, 2 * CB + w + 8 * b, p);
-  bf16x8 fa[PF];  // phase 2's ring (Q / K weights of channel block 4 ch + w % 4)
+    for (int b = 0; b < NU; ++b) bw[p][b] = *frag(w + 8 * b, p);
   float* gs = (float*)(sm + R_GS);  // [32 groups][mean, rstd]
   if (tid < 256) {
     const int g = tid >> 3, l8 = tid & 7, gsz = C / 32, n_it = gsz * a.spi;
@@ -440,120 +513,84 @@ __global__ __launch_bounds__(512, 1) void attn_block_kernel(AttnBlockArgs a) {
   __syncthreads();
   // hn fragment of (token row r, k-step st): lane (rl, hh) reads channels 16 st + 8 hh ..
   auto hn_frag = [&](int r, int st) { return *(const bf16x8*)(sm + rowc(r, 2 * st + hh, C * 2)); };
-  const int tr = 32 * wt + rl;  // this wave's token / query row
+  const int tr = 32 * wt + rl;  // this wave's query row in phases 4 / 5
 
-  // The weight-streaming phases (1, 2, 5) give each wave whole 32-channel blocks over BOTH token
-  // blocks, so every weight fragment is streamed once per block (the two token-block waves of a
-  // channel group used to stream the same fragments): V^T and proj -- channel blocks w, w + 8 (NBW a
-  // wave at most); q|k -- wave w computes Q (w < 4) or K (w >= 4) of block 4 ch + w % 4. Every
-  // output's k order is unchanged.
-  // ---- 1. V^T: D[token][c] = hn Wv^T; wave w: channel blocks w + 8 b x both token blocks
+  // ---- 1. T = hn M + u and V'^T = (hn W' + b')^T: wave w takes fragment rows w + 8 b of [M | W'] (rows below CB: a
+  // 32-channel block of T, D[c][token]; the others: of V', D[token][c]) over both token blocks
+  auto is_t = [&](int b) { return 8 * b + 7 < CB || (8 * b < CB && w + 8 * b < CB); };  // (constant but for one b at C = 384 / 128)
   {
-    f32x16 acc[2][NBW];
+    f32x16 acc[2][NU];
 #pragma unroll
     for (int tb = 0; tb < 2; ++tb)
 #pragma unroll
-      for (int b = 0; b < NBW; ++b)
+      for (int b = 0; b < NU; ++b)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[tb][b][r] = 0.f;
 #pragma unroll
     for (int st = 0; st < KS; ++st) {
-      bf16x8 cur[NBW];
+      bf16x8 cur[NU];
 #pragma unroll
-      for (int b = 0; b < NBW; ++b) cur[b] = bw[st % PF][b];
-      if (st + PF < KS) {
+      for (int b = 0; b < NU; ++b) cur[b] = bw[st % PF][b];
+      if (st + PF < KS)
 #pragma unroll
-        for (int b = 0; b < NBW; ++b)
-          if (w + 8 * b < CB) bw[st % PF][b] = *frag(a.wqkv, 2 * CB + w + 8 * b, st + PF);
-      } else {
-        fa[st + PF - KS] = *frag(a.wqkv, (w >> 2) * CB + wq, st + PF - KS);
-      }
+        for (int b = 0; b < NU; ++b) bw[st % PF][b] = *frag(w + 8 * b, st + PF);
 #pragma unroll
       for (int tb = 0; tb < 2; ++tb) {
         const bf16x8 h0 = hn_frag(32 * tb + rl, st);
 #pragma unroll
-        for (int b = 0; b < NBW; ++b)
-          if (w + 8 * b < CB) acc[tb][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(h0, cur[b], acc[tb][b], 0, 0, 0);
+        for (int b = 0; b < NU; ++b) {
+          if (is_t(b)) acc[tb][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cur[b], h0, acc[tb][b], 0, 0, 0);
+          else acc[tb][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(h0, cur[b], acc[tb][b], 0, 0, 0);
+        }
       }
     }
-    // lane: channel c = 32 cb + rl (column), tokens 32 tb + 8 g + 4 hh + e (rows)
 #pragma unroll
-    for (int tb = 0; tb < 2; ++tb)
+    for (int b = 0; b < NU; ++b) {
+      const int row = w + 8 * b;
+      if (is_t(b)) {
+        // lane: token 32 tb + rl (column), channels 32 row + 8 g + 4 hh + e (rows)
 #pragma unroll
-      for (int b = 0; b < NBW; ++b) {
-        if (w + 8 * b >= CB) continue;
-        const int c = 32 * (w + 8 * b) + rl;
-        const float bv = a.bqkv[2 * C + c];
+        for (int tb = 0; tb < 2; ++tb)
 #pragma unroll
-        for (int g = 0; g < 4; ++g)
-          *(uint2*)(sm + R_VT + row64(c, 4 * tb + g) + 8 * hh) =
-              uint2{pk_bf16(acc[tb][b][4 * g] + bv, acc[tb][b][4 * g + 1] + bv), pk_bf16(acc[tb][b][4 * g + 2] + bv, acc[tb][b][4 * g + 3] + bv)};
+          for (int g = 0; g < 4; ++g) {
+            const f32x4 bu = *(const f32x4*)(a.buv + 32 * row + 8 * g + 4 * hh);
+            *(uint2*)(sm + R_T + rowc(32 * tb + rl, 4 * row + g, C * 2) + 8 * hh) =
+                uint2{pk_bf16(acc[tb][b][4 * g] + bu[0], acc[tb][b][4 * g + 1] + bu[1]),
+                      pk_bf16(acc[tb][b][4 * g + 2] + bu[2], acc[tb][b][4 * g + 3] + bu[3])};
+          }
+      } else {
+        // lane: channel c = 32 (row - CB) + rl (column), tokens 32 tb + 8 g + 4 hh + e (rows)
+        const int c = 32 * (row - CB) + rl;
+        const float bv = a.buv[C + c];
+#pragma unroll
+        for (int tb = 0; tb < 2; ++tb)
+#pragma unroll
+          for (int g = 0; g < 4; ++g)
+            *(uint2*)(sm + R_VT + row64(c, 4 * tb + g) + 8 * hh) =
+                uint2{pk_bf16(acc[tb][b][4 * g] + bv, acc[tb][b][4 * g + 1] + bv), pk_bf16(acc[tb][b][4 * g + 2] + bv, acc[tb][b][4 * g + 3] + bv)};
       }
+    }
   }
-  ATL(2);  // hn staged + V^T computed (wave's own)
-  // ---- 2. Q_c, K_c per 128-channel chunk; S^T (keys x queries) tile w (waves 0..3) in registers
+  ATL(2);  // T and V'^T computed (wave's own)
+  __syncthreads();
+  // ---- 2. S^T (keys x queries) = hn T^T over all C channels: tile w (waves 0..3) in registers
   f32x16 sacc;
 #pragma unroll
   for (int r = 0; r < 16; ++r) sacc[r] = 0.f;
-  char* const Qc = sm + R_QK;
-  char* const Kc = sm + R_QK + S * 256;
-  for (int ch = 0; ch < NCH; ++ch) {
-    {  // wave w: Q_c (w < 4) or K_c (w >= 4), channel block 4 ch + w % 4, both token blocks
-      const int isk = w >> 2, cb = isk * CB + 4 * ch + wq;
-      f32x16 aa[2];
+  if (w < 4) {
+    const int key = 32 * (w >> 1) + rl, qry = 32 * (w & 1) + rl;
 #pragma unroll
-      for (int tb = 0; tb < 2; ++tb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) aa[tb][r] = 0.f;
-#pragma unroll
-      for (int st = 0; st < KS; ++st) {
-        const bf16x8 w_ = fa[st % PF];
-        if (st + PF < KS) fa[st % PF] = *frag(a.wqkv, cb, st + PF);
-#pragma unroll
-        for (int tb = 0; tb < 2; ++tb) {
-          const bf16x8 h0 = hn_frag(32 * tb + rl, st);
-          aa[tb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w_, h0, aa[tb], 0, 0, 0);
-        }
-      }
-      // lane: token 32 tb + rl (column), channels 32 wq + 8 g + 4 hh + e of the chunk (rows)
-      char* const dstc = isk ? Kc : Qc;
-#pragma unroll
-      for (int tb = 0; tb < 2; ++tb)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int cq = 128 * ch + 32 * wq + 8 * g + 4 * hh, tk = 32 * tb + rl;
-          const f32x4 bq = *(const f32x4*)(a.bqkv + isk * C + cq);
-          *(uint2*)(dstc + rowc(tk, 4 * wq + g, 256) + 8 * hh) =
-              uint2{pk_bf16(aa[tb][4 * g] + bq[0], aa[tb][4 * g + 1] + bq[1]), pk_bf16(aa[tb][4 * g + 2] + bq[2], aa[tb][4 * g + 3] + bq[3])};
-        }
-      // the next chunk's first PF fragments, in flight through this chunk's barriers and score MFMAs
-      if (ch + 1 < NCH)
-#pragma unroll
-        for (int p = 0; p < PF; ++p) fa[p] = *frag(a.wqkv, cb + 4, p);
+    for (int st = 0; st < KS; ++st) {
+      const bf16x8 kf = hn_frag(key, st);
+      const bf16x8 qf = *(const bf16x8*)(sm + R_T + rowc(qry, 2 * st + hh, C * 2));
+      sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf, sacc, 0, 0, 0);
     }
-    __syncthreads();
-    if (w < 4) {
-      const int key = 32 * (w >> 1) + rl, qry = 32 * (w & 1) + rl;
-#pragma unroll
-      for (int st = 0; st < 8; ++st) {
-        const bf16x8 kf = *(const bf16x8*)(Kc + rowc(key, 2 * st + hh, 256));
-        const bf16x8 qf = *(const bf16x8*)(Qc + rowc(qry, 2 * st + hh, 256));
-        sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf, sacc, 0, 0, 0);
-      }
-    }
-    __syncthreads();  // Q_c / K_c are rewritten by the next chunk
   }
+  __syncthreads();  // T is dead: the scores and P take its space
   ATL(3);  // scores done
-  // phase 5's first PF weight fragments, in flight through the softmax and PV phases
-  bf16x8 aw[PF][NBW];
-#pragma unroll
-  for (int p = 0; p < PF; ++p)
-#pragma unroll
-    for (int b = 0; b < NBW; ++b)
-      if (w + 8 * b < CB) aw[p][b] = *frag(a.wp, w + 8 * b, p);
   // ---- 3. softmax over keys: S[query][key] fp32 through LDS, P [query][key] bf16
-  float* const Sm = (float*)(sm + R_QK);              // [64][64 + 4]
-  char* const Pm = sm + R_QK + S * (S + 4) * 4;       // [64][64] bf16, 128-B rows
+  float* const Sm = (float*)(sm + R_T);              // [64][64 + 4]
+  char* const Pm = sm + R_T + S * (S + 4) * 4;       // [64][64] bf16, 128-B rows
   if (w < 4) {
     const int qry = 32 * (w & 1) + rl;
 #pragma unroll
@@ -587,131 +624,32 @@ __global__ __launch_bounds__(512, 1) void attn_block_kernel(AttnBlockArgs a) {
   }
   __syncthreads();
   ATL(4);  // softmax done
-  // ---- 4. O^T = V^T P^T: D[c][query], wave: channel blocks CBW wq .. x query block wt -> O [token][C]
-  {
-    f32x16 acc[CBW];
+  // ---- 4. O^T = V'^T P^T: D[c][query], wave: channel blocks CBW wq .. x query block wt, in registers
+  f32x16 oacc[CBW];
 #pragma unroll
-    for (int b = 0; b < CBW; ++b)
+  for (int b = 0; b < CBW; ++b)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
+    for (int r = 0; r < 16; ++r) oacc[b][r] = 0.f;
 #pragma unroll
-    for (int st = 0; st < 4; ++st) {
-      const bf16x8 p0 = *(const bf16x8*)(Pm + row64(tr, 2 * st + hh));
+  for (int st = 0; st < 4; ++st) {
+    const bf16x8 p0 = *(const bf16x8*)(Pm + row64(tr, 2 * st + hh));
 #pragma unroll
-      for (int b = 0; b < CBW; ++b) {
-        const int c = 32 * (CBW * wq + b) + rl;
-        const bf16x8 vf = *(const bf16x8*)(sm + R_VT + row64(c, 2 * st + hh));
-        acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, p0, acc[b], 0, 0, 0);
-      }
+    for (int b = 0; b < CBW; ++b) {
+      const int c = 32 * (CBW * wq + b) + rl;
+      const bf16x8 vf = *(const bf16x8*)(sm + R_VT + row64(c, 2 * st + hh));
+      oacc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, p0, oacc[b], 0, 0, 0);
     }
-    // hn is dead since phase 2: O goes to its rows. lane: query tr, channels 32 cb + 8 g + 4 hh + e
-#pragma unroll
-    for (int b = 0; b < CBW; ++b)
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-        *(uint2*)(sm + rowc(tr, 4 * (CBW * wq + b) + g, C * 2) + 8 * hh) =
-            uint2{pk_bf16(acc[b][4 * g], acc[b][4 * g + 1]), pk_bf16(acc[b][4 * g + 2], acc[b][4 * g + 3])};
   }
-  __syncthreads();
   ATL(5);  // PV done
-  // ---- 5. out = x + O Wp^T + bp: D[c'][token], wave w: blocks w + 8 b x both token blocks
+  // ---- 5. out = x + O + bp from the PV accumulators (lane: query tr, channels 32 cb + 8 g + 4 hh + e)
   float* const spart = (float*)(sm + R_ST);  // [token block][2][C]: the two token blocks' statistics
-  {
-    f32x16 acc[2][NBW];
+  bf16_t* out = a.out + (size_t)img * S * C;
 #pragma unroll
-    for (int tb = 0; tb < 2; ++tb)
-#pragma unroll
-      for (int b = 0; b < NBW; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[tb][b][r] = 0.f;
-#pragma unroll
-    for (int st = 0; st < KS; ++st) {
-      bf16x8 cur[NBW];
-#pragma unroll
-      for (int b = 0; b < NBW; ++b) cur[b] = aw[st % PF][b];
-      if (st + PF < KS)
-#pragma unroll
-        for (int b = 0; b < NBW; ++b)
-          if (w + 8 * b < CB) aw[st % PF][b] = *frag(a.wp, w + 8 * b, st + PF);
-#pragma unroll
-      for (int tb = 0; tb < 2; ++tb) {
-        const bf16x8 o0 = hn_frag(32 * tb + rl, st);
-#pragma unroll
-        for (int b = 0; b < NBW; ++b)
-          if (w + 8 * b < CB) acc[tb][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cur[b], o0, acc[tb][b], 0, 0, 0);
-      }
-    }
-    bf16_t* out = a.out + (size_t)img * S * C;
-#pragma unroll
-    for (int tb = 0; tb < 2; ++tb) {
-      const int tk = 32 * tb + rl;  // this lane's token
-#pragma unroll
-      for (int b = 0; b < NBW; ++b) {
-        if (w + 8 * b >= CB) continue;
-        const int cb = w + 8 * b;
-        float v[32];
-        uint32_t wv[4][2];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int c = 32 * cb + 8 * g + 4 * hh;
-          const f32x4 bb = *(const f32x4*)(a.bp + c);
-          const uint2 rr = *(const uint2*)(x + (size_t)tk * C + c);
-          const float v0 = acc[tb][b][4 * g + 0] + bb[0] + __uint_as_float(rr.x << 16);
-          const float v1 = acc[tb][b][4 * g + 1] + bb[1] + __uint_as_float(rr.x & 0xffff0000u);
-          const float v2 = acc[tb][b][4 * g + 2] + bb[2] + __uint_as_float(rr.y << 16);
-          const float v3 = acc[tb][b][4 * g + 3] + bb[3] + __uint_as_float(rr.y & 0xffff0000u);
-          wv[g][0] = pk_bf16(v0, v1);
-          wv[g][1] = pk_bf16(v2, v3);
-          const float r0 = __uint_as_float(wv[g][0] << 16), r1 = __uint_as_float(wv[g][0] & 0xffff0000u);
-          const float r2 = __uint_as_float(wv[g][1] << 16), r3 = __uint_as_float(wv[g][1] & 0xffff0000u);
-          v[4 * g + 0] = r0; v[16 + 4 * g + 0] = r0 * r0;
-          v[4 * g + 1] = r1; v[16 + 4 * g + 1] = r1 * r1;
-          v[4 * g + 2] = r2; v[16 + 4 * g + 2] = r2 * r2;
-          v[4 * g + 3] = r3; v[16 + 4 * g + 3] = r3 * r3;
-        }
-#pragma unroll
-        for (int gp = 0; gp < 4; gp += 2) {
-          u32x4 o;
-#pragma unroll
-          for (int d = 0; d < 2; ++d) {
-            const auto sw = __builtin_amdgcn_permlane32_swap(wv[gp][d], wv[gp + 1][d], false, false);
-            o[d] = sw[0];
-            o[2 + d] = sw[1];
-          }
-          *(u32x4*)(out + (size_t)tk * C + 32 * cb + 8 * (gp + hh)) = o;
-        }
-        if (a.out_stats) {  // this token block's 32 lanes: butterfly, then the two blocks summed in order
-          auto xchg = [](float xf, auto wc) {
-            constexpr int wd = decltype(wc)::value;
-            const int xi = __builtin_bit_cast(int, xf);
-            int r;
-            if constexpr (wd == 1) r = __builtin_amdgcn_update_dpp(0, xi, 0xB1, 0xF, 0xF, false);
-            else if constexpr (wd == 2) r = __builtin_amdgcn_update_dpp(0, xi, 0x4E, 0xF, 0xF, false);
-            else if constexpr (wd == 8) r = __builtin_amdgcn_update_dpp(0, xi, 0x128, 0xF, 0xF, false);
-            else r = __builtin_amdgcn_ds_swizzle(xi, 0x1F | (wd << 10));
-            return __builtin_bit_cast(float, r);
-          };
-          auto halve = [&](auto wc) {
-            constexpr int wd = decltype(wc)::value;
-            const bool up = (rl & wd) != 0;
-#pragma unroll
-            for (int ii = 0; ii < wd; ++ii) {
-              const float lo = v[ii], hi = v[ii + wd];
-              v[ii] = (up ? hi : lo) + xchg(up ? lo : hi, wc);
-            }
-          };
-          halve(std::integral_constant<int, 16>{});
-          halve(std::integral_constant<int, 8>{});
-          halve(std::integral_constant<int, 4>{});
-          halve(std::integral_constant<int, 2>{});
-          halve(std::integral_constant<int, 1>{});
-          const int e = rl & 15, co = 32 * cb + 8 * (e >> 2) + 4 * hh + (e & 3);
-          spart[(tb * 2 + (rl >> 4)) * C + co] = v[0];
-        }
-      }
-    }
+  for (int b = 0; b < CBW; ++b) {
+    const int cb = CBW * wq + b;
+    attn_out_tile(oacc[b], x, out, a.bp, C, tr, 32 * cb, rl, hh, false, a.out_stats ? spart + wt * 2 * C + 32 * cb : nullptr, C);
   }
-  ATL(6);  // proj + epilogue (wave's own)
+  ATL(6);  // epilogue (wave's own)
   if (a.out_stats) {
     __syncthreads();
     for (int i = tid; i < 2 * C; i += 512)  // (sum | sum of squares) x channel: token block 0 + block 1
@@ -723,24 +661,26 @@ __global__ __launch_bounds__(512, 1) void attn_block_kernel(AttnBlockArgs a) {
 // ---------------------------------------------------------------------------- fused AttnBlock over G blocks
 // attn_block_split_kernel<C, G>: attn_block_kernel's image spread over G blocks for small batches (the
 // 8-GPU shard runs N = 32: one block per image left 224 of 256 CUs idle while every block streamed all
-// 1.2 MB of the block's weights). Block (img, g) owns channel blocks [g CBg, (g+1) CBg),
-// CBg = C / 32 / G, and streams only those weight rows:
-//   0. GroupNorm + hn as attn_block_kernel (every block: hn is the K operand of every projection);
-//   1. its V^T, Q, K channel slices (hn W^T + b) -> LDS;
-//   2. its partial scores S_g^T = K_g Q_g^T (keys x queries, fp32) -> write-through slab, counter;
-//      every block waits for the image's G partials, sums them in g order 0..G-1 (the same bits in every
-//      block, whichever arrives last) -> softmax -> P (bf16), as attn_block_kernel;
-//   3. O^T of its channels = V_g^T P^T -> write-through slab [img][token][C], counter; waits for all G;
-//   4. out = x + O Wp^T + bp for its output channels (full O from the slab), its channels' GroupNorm
-//      statistics (per channel: no cross-block sum).
-// Roundings as attn_block_kernel (hn, q / k / v, P, O in bf16); only S is summed in another order (G
+// of the block's weights). Block (img, g) owns channel blocks [g CBg, (g+1) CBg),
+// CBg = C / 32 / G, and streams only those rows of M and W' (4 C^2 / G bytes):
+//   0. GroupNorm + hn as attn_block_kernel (every block: hn is the K operand of both projections and the
+//      key operand of the scores);
+//   1. its channel slices of V'^T and T (hn W + b) -> LDS;
+//   2. its partial scores S_g^T = hn_g T_g^T (keys x queries over its channels, fp32) -> write-through slab,
+//      counter; every block waits for the image's G partials, sums them in g order 0..G-1 (the same bits in
+//      every block, whichever arrives last) -> softmax -> P (bf16), as attn_block_kernel;
+//   3. O^T of its channels = V'_g^T P^T in registers -> out = x + O + bp for those channels and their
+//      GroupNorm statistics (per channel: no cross-block sum). The output needs no other block's O: one
+//      hand-off a launch.
+// Roundings as attn_block_kernel (hn, T, V', P in bf16); only S is summed in another order (G
 // partial sums), so it agrees with attn_block_kernel within bf16 tolerance, not bit for bit.
-// Hand-offs: MI355X_MICROARCH.md visibility table, row 1 (sc1 stores; every storing wave waits
+// Hand-off: MI355X_MICROARCH.md visibility table, row 1 (sc1 stores; every storing wave waits
 // vmcnt(0); a workgroup barrier; one agent-scope atomic add per block; one lane polls with sc1 loads
-// (s_sleep, bounded); a workgroup barrier; every load of the handed-off bytes an sc1 load). The counters
-// only grow, by 12 per launch (12 / G per block), so a block's target -- the next multiple of 12 above the
-// value its own add returned -- holds whatever G earlier launches used (launches on a stream never overlap). Waiting blocks need the whole grid resident: the host launches it only when
-// n * G <= CUs (one 512-thread block per CU).
+// (s_sleep, bounded); a workgroup barrier; every load of the handed-off bytes an sc1 load). An image's counter
+// only grows: a launch's G blocks add 12 / G each, once, so between launches (launches on a stream never
+// overlap) it is a multiple of 12 whatever G earlier launches used, and a block's target -- the next multiple
+// of 12 above the value its own add returned -- is reached exactly when the launch's G blocks have added.
+// Waiting blocks need the whole grid resident: the host launches it only when n * G <= CUs (one 512-thread block per CU).
 #ifndef ITSD_ATTN_SPLIT_PF
 #define ITSD_ATTN_SPLIT_PF 8
 #endif
@@ -748,8 +688,8 @@ template <int C, int G>
 __global__ __launch_bounds__(512, 1) void attn_block_split_kernel(AttnBlockArgs a) {
   constexpr int S = 64, KS = C / 16, CB = C / 32, CBg = CB / G, CW = CBg * 32, PF = ITSD_ATTN_SPLIT_PF;
   static_assert(CB % G == 0 && C % 128 == 0 && 12 % G == 0, "G divides the channel blocks and 12");
-  constexpr int QROW = CW * 2 + 16;  // Q_g / K_g row (bytes): padded so 16-B reads of 16 rows are conflict-free
-  constexpr int R_VT = S * C * 2, R_Q = R_VT + CW * 128, R_K = R_Q + S * QROW, R_SM = R_K + S * QROW;
+  constexpr int QROW = CW * 2 + 16;  // T_g row (bytes): padded so 16-B reads of 16 rows are conflict-free
+  constexpr int R_VT = S * C * 2, R_T = R_VT + CW * 128, R_SM = R_T + S * QROW;
   constexpr int R_PM = R_SM + S * (S + 4) * 4, R_GS = R_PM + S * 128, R_ST = R_GS + 32 * 2 * 4;
   __shared__ __attribute__((aligned(16))) char sm[R_ST + 2 * 2 * CW * 4];
   const int tid = threadIdx.x, lane = tid & 63, rl = lane & 31, hh = lane >> 5;
@@ -758,20 +698,20 @@ __global__ __launch_bounds__(512, 1) void attn_block_split_kernel(AttnBlockArgs 
   const bf16_t* x = a.x + (size_t)img * S * C;
   auto rowc = [](int r, int ch, int rowbytes) { return r * rowbytes + ((ch ^ (r & 15)) << 4); };
   auto row64 = [](int r, int ch) { return r * 128 + ((ch ^ ((r >> 1) & 7)) << 4); };
-  auto frag = [&](const bf16_t* W, int cb, int st) -> const bf16x8* {
-    return (const bf16x8*)((const char*)W + ((size_t)cb * KS + st) * 1024 + lane * 16);
+  auto frag = [&](int row, int st) -> const bf16x8* {
+    return (const bf16x8*)((const char*)a.wmv + ((size_t)row * KS + st) * 1024 + lane * 16);
   };
-  // projection unit u = kind * CBg + cbl (kind 0 V, 1 Q, 2 K): its fragment row of the packed q|k|v matrix
+  // projection unit u = kind * CBg + cbl (kind 0 V', 1 T): its fragment row of the packed [M | W'] matrix
   auto frow_of = [&](int u) {
     const int kind = u / CBg, cb = g * CBg + u - kind * CBg;
-    return kind == 0 ? 2 * CB + cb : (kind - 1) * CB + cb;
+    return kind == 0 ? CB + cb : cb;
   };
   // the first PF weight fragments of this wave's first unit, in flight before anything else (they depend
   // on no earlier kernel: their latency hides behind the x loads and the GroupNorm)
   bf16x8 fw[PF];
-  if (w < 3 * CBg) {
+  if (w < 2 * CBg) {
 #pragma unroll
-    for (int p = 0; p < PF; ++p) fw[p] = *frag(a.wqkv, frow_of(w), p);
+    for (int p = 0; p < PF; ++p) fw[p] = *frag(frow_of(w), p);
   }
   // ---- 0. GroupNorm statistics and hn (attn_block_kernel's phase 0)
   constexpr int XU = S * (C / 8) / 512;
@@ -828,7 +768,7 @@ __global__ __launch_bounds__(512, 1) void attn_block_split_kernel(AttnBlockArgs 
   auto hn_frag = [&](int r, int st) { return *(const bf16x8*)(sm + rowc(r, 2 * st + hh, C * 2)); };
   // weight-stream unit: one 32-channel block of a projection over both token blocks (fragments loaded once);
   // fw holds the unit's first PF fragments when it is called
-  auto unit = [&](const bf16_t* W, int frow, f32x16 (&acc)[2], auto vform) __attribute__((always_inline)) {
+  auto unit = [&](int frow, f32x16 (&acc)[2], auto vform) __attribute__((always_inline)) {
     constexpr bool VF = decltype(vform)::value;  // true: D[token][c] (A = hn); false: D[c][token] (A = W)
 #pragma unroll
     for (int tb = 0; tb < 2; ++tb)
@@ -837,7 +777,7 @@ __global__ __launch_bounds__(512, 1) void attn_block_split_kernel(AttnBlockArgs 
 #pragma unroll
     for (int st = 0; st < KS; ++st) {
       const bf16x8 cur = fw[st % PF];
-      if (st + PF < KS) fw[st % PF] = *frag(W, frow, st + PF);
+      if (st + PF < KS) fw[st % PF] = *frag(frow, st + PF);
 #pragma unroll
       for (int tb = 0; tb < 2; ++tb) {
         const bf16x8 h0 = hn_frag(32 * tb + rl, st);
@@ -846,18 +786,18 @@ __global__ __launch_bounds__(512, 1) void attn_block_split_kernel(AttnBlockArgs 
       }
     }
   };
-  // ---- 1. this block's V^T, Q, K slices: units u = kind * CBg + cbl (kind 0 V, 1 Q, 2 K)
-  for (int u = w; u < 3 * CBg; u += 8) {
+  // ---- 1. this block's V'^T and T slices: units u = kind * CBg + cbl (kind 0 V', 1 T)
+  for (int u = w; u < 2 * CBg; u += 8) {
     const int kind = u / CBg, cbl = u - kind * CBg, cb = g * CBg + cbl;
     f32x16 acc[2];
-    if (u != w) {  // a wave's later units (G <= 4): their first fragments now
+    if (u != w) {  // a wave's second unit (G = 2): its first fragments now
 #pragma unroll
-      for (int p = 0; p < PF; ++p) fw[p] = *frag(a.wqkv, frow_of(u), p);
+      for (int p = 0; p < PF; ++p) fw[p] = *frag(frow_of(u), p);
     }
     if (kind == 0) {
-      unit(a.wqkv, 2 * CB + cb, acc, std::true_type{});
-      // lane: channel 32 cb + rl, tokens 32 tb + 8 q + 4 hh + e -> V^T row (local channel), 4 tokens a store
-      const float bv = a.bqkv[2 * C + 32 * cb + rl];
+      unit(CB + cb, acc, std::true_type{});
+      // lane: channel 32 cb + rl, tokens 32 tb + 8 q + 4 hh + e -> V'^T row (local channel), 4 tokens a store
+      const float bv = a.buv[C + 32 * cb + rl];
 #pragma unroll
       for (int tb = 0; tb < 2; ++tb)
 #pragma unroll
@@ -865,22 +805,21 @@ __global__ __launch_bounds__(512, 1) void attn_block_split_kernel(AttnBlockArgs 
           *(uint2*)(sm + R_VT + row64(32 * cbl + rl, 4 * tb + q) + 8 * hh) =
               uint2{pk_bf16(acc[tb][4 * q] + bv, acc[tb][4 * q + 1] + bv), pk_bf16(acc[tb][4 * q + 2] + bv, acc[tb][4 * q + 3] + bv)};
     } else {
-      unit(a.wqkv, (kind - 1) * CB + cb, acc, std::false_type{});
-      // lane: token 32 tb + rl, channels 32 cb + 8 q + 4 hh + e -> Q_g / K_g [token][local channel]
-      char* dst = sm + (kind == 1 ? R_Q : R_K);
+      unit(cb, acc, std::false_type{});
+      // lane: token 32 tb + rl, channels 32 cb + 8 q + 4 hh + e -> T_g [token][local channel]
 #pragma unroll
       for (int tb = 0; tb < 2; ++tb)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int cl = 32 * cbl + 8 * q + 4 * hh;
-          const f32x4 bq = *(const f32x4*)(a.bqkv + (kind - 1) * C + g * CW + cl);
-          *(uint2*)(dst + (32 * tb + rl) * QROW + cl * 2) =
-              uint2{pk_bf16(acc[tb][4 * q] + bq[0], acc[tb][4 * q + 1] + bq[1]), pk_bf16(acc[tb][4 * q + 2] + bq[2], acc[tb][4 * q + 3] + bq[3])};
+          const f32x4 bu = *(const f32x4*)(a.buv + g * CW + cl);
+          *(uint2*)(sm + R_T + (32 * tb + rl) * QROW + cl * 2) =
+              uint2{pk_bf16(acc[tb][4 * q] + bu[0], acc[tb][4 * q + 1] + bu[1]), pk_bf16(acc[tb][4 * q + 2] + bu[2], acc[tb][4 * q + 3] + bu[3])};
         }
     }
   }
   __syncthreads();
-  // ---- 2. partial scores S_g^T[key][query] over this block's channels (waves 0..3: tile w), write-through
+  // ---- 2. partial scores S_g^T[key][query] = hn_g T_g^T over this block's channels (waves 0..3: tile w), write-through
   const uint32_t sp_bytes = (uint32_t)std::min<long long>((long long)a.n * G * 4 * 1024 * 4, 0x7fffffffLL);
   const __amdgpu_buffer_rsrc_t sp = __builtin_amdgcn_make_buffer_rsrc(a.spart, (short)0, (int)sp_bytes, 0x00020000);
   if (w < 4) {
@@ -890,8 +829,8 @@ __global__ __launch_bounds__(512, 1) void attn_block_split_kernel(AttnBlockArgs 
     for (int r = 0; r < 16; ++r) sacc[r] = 0.f;
 #pragma unroll
     for (int st = 0; st < CW / 16; ++st) {
-      const bf16x8 kf = *(const bf16x8*)(sm + R_K + key * QROW + (2 * st + hh) * 16);
-      const bf16x8 qf = *(const bf16x8*)(sm + R_Q + qry * QROW + (2 * st + hh) * 16);
+      const bf16x8 kf = hn_frag(key, g * (CW / 16) + st);
+      const bf16x8 qf = *(const bf16x8*)(sm + R_T + qry * QROW + (2 * st + hh) * 16);
       sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf, sacc, 0, 0, 0);
     }
     const uint32_t off = (uint32_t)((((size_t)img * G + g) * 4 + w) * 1024 + lane * 16) * 4;
@@ -902,35 +841,30 @@ __global__ __launch_bounds__(512, 1) void attn_block_split_kernel(AttnBlockArgs 
                                              sp, off + q * 16, 0, 16);
   }
   // hand-off: this block's stores drained, one add, one lane polls until the image's G blocks have added
-  // Every launch adds exactly 12 to each counter (12 / G per block; G in {2, 4, 6}), so between launches a
-  // counter is a multiple of 12 whatever G earlier launches used, and a block's target is the next one.
-  // `during` runs between the barriers while lane 0 of wave 0 polls (work that needs no handed-off byte)
+  // (the counter rule: the comment above the kernel).
   // Fail loudly: a wait that exhausts its poll bound (a grid that is not co-resident -- another process on
   // the GPU, a CU mask) would read partial slabs; the block then keeps the counter protocol (every block
   // still adds, so later launches' targets hold), sets bit 0 of the status word *a.err (the sampler / forward
   // report ITSD_ERR_HANDOFF) and writes NaN to its output channels (the NaN check of Diffusion.py:100 fires too)
   __shared__ int hbad;
   if (tid == 0) hbad = 0;
-  auto handoff = [&](int* cnt, auto during) __attribute__((always_inline)) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    during();
-    if (tid == 0) {
-      const int old = __hip_atomic_fetch_add(cnt, 12 / G, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const int target = (old / 12 + 1) * 12;
-      int v = __hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      for (int it = 0; v < target && it < a.spin_bound; ++it) {  // bounded: a grid that is not co-resident cannot hang the GPU
-        __builtin_amdgcn_s_sleep(2);
-        v = __hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      if (v < target) {
-        hbad = 1;
-        __hip_atomic_fetch_or(a.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (tid == 0) {
+    int* const cnt = a.sync + img;
+    const int old = __hip_atomic_fetch_add(cnt, 12 / G, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int target = (old / 12 + 1) * 12;
+    int v = __hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (int it = 0; v < target && it < a.spin_bound; ++it) {  // bounded: a grid that is not co-resident cannot hang the GPU
+      __builtin_amdgcn_s_sleep(2);
+      v = __hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    __syncthreads();
-  };
-  handoff(a.sync + 2 * img, [] {});
+    if (v < target) {
+      hbad = 1;
+      __hip_atomic_fetch_or(a.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+  __syncthreads();
   // every block: S = sum of the G partials in g order (waves 0..3, their tile), scaled -> Sm [query][key]
   float* const Sm = (float*)(sm + R_SM);
   char* const Pm = sm + R_PM;
@@ -979,11 +913,13 @@ __global__ __launch_bounds__(512, 1) void attn_block_split_kernel(AttnBlockArgs 
               pk_bf16(v[6] * inv, v[7] * inv)};
   }
   __syncthreads();
-  // ---- 3. O^T of this block's channels = V_g^T P^T: tiles (local channel block, query block) -> O slab
-  const uint32_t o_bytes = (uint32_t)std::min<long long>((long long)a.n * S * C * 2, 0x7fffffffLL);
-  const __amdgpu_buffer_rsrc_t osl = __builtin_amdgcn_make_buffer_rsrc(a.oslab, (short)0, (int)o_bytes, 0x00020000);
+  // ---- 3. O^T of this block's channels = V'_g^T P^T: tiles (local channel block, query block), and from each
+  // tile's registers out = x + O + bp with the channels' statistics
+  float* const spart = (float*)(sm + R_ST);  // [token block][2][CW]
+  bf16_t* out = a.out + (size_t)img * S * C;
+  const bool hb = hbad != 0;  // (a failed hand-off: NaN outputs)
   for (int tile = w; tile < 2 * CBg; tile += 8) {
-    const int cbl = tile >> 1, q = 32 * (tile & 1) + rl;
+    const int cbl = tile >> 1, tb = tile & 1, q = 32 * tb + rl;
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
@@ -993,101 +929,9 @@ __global__ __launch_bounds__(512, 1) void attn_block_split_kernel(AttnBlockArgs 
       const bf16x8 vf = *(const bf16x8*)(sm + R_VT + row64(32 * cbl + rl, 2 * st + hh));
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, p0, acc, 0, 0, 0);
     }
-    // lane: query q, channels g CW + 32 cbl + 8 r4 + 4 hh + e (4 consecutive: one 8-B store)
-    typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
-#pragma unroll
-    for (int r4 = 0; r4 < 4; ++r4) {
-      const int c = g * CW + 32 * cbl + 8 * r4 + 4 * hh;
-      __builtin_amdgcn_raw_buffer_store_b64(u32x2{pk_bf16(acc[4 * r4], acc[4 * r4 + 1]), pk_bf16(acc[4 * r4 + 2], acc[4 * r4 + 3])},
-                                            osl, (uint32_t)((((size_t)img * S + q) * C + c) * 2), 0, 16);
-    }
-  }
-  // (the proj unit's first fragments go out while the block waits for the other slices)
-  handoff(a.sync + 2 * img + 1, [&] {
-    if (w < CBg) {
-#pragma unroll
-      for (int p = 0; p < PF; ++p) fw[p] = *frag(a.wp, g * CBg + w, p);
-    }
-  });
-  // the full O [token][C] (every block's slice) -> hn's rows (hn is dead since phase 1)
-  for (int i = tid; i < S * (C / 8); i += 512) {
-    const int t = i / (C / 8), ch = i - t * (C / 8);
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(osl, (uint32_t)((((size_t)img * S + t) * C + ch * 8) * 2), 0, 16);
-    *(u32x4*)(sm + rowc(t, ch, C * 2)) = v;
-  }
-  __syncthreads();
-  // ---- 4. out = x + O Wp^T + bp for this block's output channels; statistics of its channels
-  float* const spart = (float*)(sm + R_ST);  // [token block][2][CW]
-  bf16_t* out = a.out + (size_t)img * S * C;
-  const bool hb = hbad != 0;  // (a failed hand-off, see handoff: NaN outputs)
-  for (int cbl = w; cbl < CBg; cbl += 8) {  // (CBg <= 6: one unit a wave, its fragments loaded above)
-    const int cb = g * CBg + cbl;
-    f32x16 acc[2];
-    unit(a.wp, cb, acc, std::false_type{});  // D[c'][token]
-#pragma unroll
-    for (int tb = 0; tb < 2; ++tb) {
-      const int tk = 32 * tb + rl;
-      float v[32];
-      uint32_t wv[4][2];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int c = 32 * cb + 8 * q + 4 * hh;
-        const f32x4 bb = *(const f32x4*)(a.bp + c);
-        const uint2 rr = *(const uint2*)(x + (size_t)tk * C + c);
-        const float nan = __builtin_nanf("");  // (a failed hand-off: every output channel NaN)
-        const float v0 = hb ? nan : acc[tb][4 * q + 0] + bb[0] + __uint_as_float(rr.x << 16);
-        const float v1 = hb ? nan : acc[tb][4 * q + 1] + bb[1] + __uint_as_float(rr.x & 0xffff0000u);
-        const float v2 = hb ? nan : acc[tb][4 * q + 2] + bb[2] + __uint_as_float(rr.y << 16);
-        const float v3 = hb ? nan : acc[tb][4 * q + 3] + bb[3] + __uint_as_float(rr.y & 0xffff0000u);
-        wv[q][0] = pk_bf16(v0, v1);
-        wv[q][1] = pk_bf16(v2, v3);
-        const float r0 = __uint_as_float(wv[q][0] << 16), r1 = __uint_as_float(wv[q][0] & 0xffff0000u);
-        const float r2 = __uint_as_float(wv[q][1] << 16), r3 = __uint_as_float(wv[q][1] & 0xffff0000u);
-        v[4 * q + 0] = r0; v[16 + 4 * q + 0] = r0 * r0;
-        v[4 * q + 1] = r1; v[16 + 4 * q + 1] = r1 * r1;
-        v[4 * q + 2] = r2; v[16 + 4 * q + 2] = r2 * r2;
-        v[4 * q + 3] = r3; v[16 + 4 * q + 3] = r3 * r3;
-      }
-#pragma unroll
-      for (int gp = 0; gp < 4; gp += 2) {
-        u32x4 o;
-#pragma unroll
-        for (int d = 0; d < 2; ++d) {
-          const auto swp = __builtin_amdgcn_permlane32_swap(wv[gp][d], wv[gp + 1][d], false, false);
-          o[d] = swp[0];
-          o[2 + d] = swp[1];
-        }
-        *(u32x4*)(out + (size_t)tk * C + 32 * cb + 8 * (gp + hh)) = o;
-      }
-      if (a.out_stats) {
-        auto xchg = [](float xf, auto wc) {
-          constexpr int wd = decltype(wc)::value;
-          const int xi = __builtin_bit_cast(int, xf);
-          int r;
-          if constexpr (wd == 1) r = __builtin_amdgcn_update_dpp(0, xi, 0xB1, 0xF, 0xF, false);
-          else if constexpr (wd == 2) r = __builtin_amdgcn_update_dpp(0, xi, 0x4E, 0xF, 0xF, false);
-          else if constexpr (wd == 8) r = __builtin_amdgcn_update_dpp(0, xi, 0x128, 0xF, 0xF, false);
-          else r = __builtin_amdgcn_ds_swizzle(xi, 0x1F | (wd << 10));
-          return __builtin_bit_cast(float, r);
-        };
-        auto halve = [&](auto wc) {
-          constexpr int wd = decltype(wc)::value;
-          const bool up = (rl & wd) != 0;
-#pragma unroll
-          for (int ii = 0; ii < wd; ++ii) {
-            const float lo = v[ii], hi = v[ii + wd];
-            v[ii] = (up ? hi : lo) + xchg(up ? lo : hi, wc);
-          }
-        };
-        halve(std::integral_constant<int, 16>{});
-        halve(std::integral_constant<int, 8>{});
-        halve(std::integral_constant<int, 4>{});
-        halve(std::integral_constant<int, 2>{});
-        halve(std::integral_constant<int, 1>{});
-        const int e = rl & 15, col = 32 * cbl + 8 * (e >> 2) + 4 * hh + (e & 3);
-        spart[(tb * 2 + (rl >> 4)) * CW + col] = v[0];
-      }
-    }
+    // lane: query q, channels g CW + 32 cbl + 8 r4 + 4 hh + e
+    attn_out_tile(acc, x, out, a.bp, C, q, g * CW + 32 * cbl, rl, hh, hb,
+                  a.out_stats ? spart + tb * 2 * CW + 32 * cbl : nullptr, CW);
   }
   if (a.out_stats) {
     __syncthreads();
@@ -1122,7 +966,7 @@ int attn_split_g(int n, int C) {
 }
 
 hipError_t launch_attn_block(const AttnBlockArgs& a, int C, hipStream_t s) {
-  if (a.spart && a.oslab && a.sync && a.S == 64) {
+  if (a.spart && a.sync && a.S == 64) {
     const int G = attn_split_g(a.n, C);
     if (G == 6) ITSD_LAUNCH((attn_block_split_kernel<384, 6>), dim3(a.n * 6), dim3(512), 0, s, a);
     else if (G == 4) ITSD_LAUNCH((attn_block_split_kernel<384, 4>), dim3(a.n * 4), dim3(512), 0, s, a);

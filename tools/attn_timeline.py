@@ -38,7 +38,7 @@ def main():
     buf = np.zeros(1024 * 128, dtype=np.uint64)
     assert L.itsd_debug_stamps_attn(buf.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong))) == 0
     st = buf.reshape(1024, 16, 8).astype(np.int64)[: min(args.n, 1024)]
-    names = ["entry", "group stats", "hn + V^T", "scores", "softmax", "PV", "proj + epilogue", "exit"]
+    names = ["entry", "group stats", "hn + T + V'^T", "scores", "softmax", "PV", "epilogue", "exit"]
     print(f"op {i} attn_block_kernel N={args.n}: {ms * 1e3:.1f} us/launch")
     for w in (0, 4):
         rel = (st[:, w, :] - st[:, w, :1]) / 100.0
