@@ -16,6 +16,10 @@
  *                                   (Diffusion/Diffusion.py:51-65, DiffusionCondition.py:57-73)
  *   itsd_sampler_run             <- GaussianDiffusionSampler.forward loop
  *                                   (Diffusion.py:84-102, DiffusionCondition.py:89-105)
+ *   itsd_set_schedule_x0         <- (no reference counterpart: it has no few-step sampler) a schedule of K rows, row k
+ *                                   run at timestep tau[k], stepped by DDIM(eta) written through the x_0 estimate
+ *                                   (optionally clipped, Ho et al.'s clip_denoised). Opt-in: itsd_set_schedule's
+ *                                   ancestral form stays the default and the parity contract
  *   itsd_sampler_predict_x0      <- (no reference counterpart) the x_0 estimate of a half-denoised state, what a
  *                                   verifier can score mid-trajectory: the branching PathSearch its docstring
  *                                   describes (search/search_algorithm.py:238-250; its code, :307-312, is a placeholder)
@@ -119,17 +123,47 @@ int itsd_unet_representation(itsd_unet* u, float* repr, int n, void* stream);
 int itsd_set_schedule(itsd_unet* u, int T, const float* coeff1, const float* coeff2,
                       const float* sqrt_var, float w);
 
+/* The x0-form schedule. Row k of K evaluates the model at timestep tau[k] (strictly increasing, >= 0) and steps
+ *     x0 = a0[k] x - b0[k] eps,  clipped to [-1, 1] iff clip_x0;   x' = (c0[k] x0 + cx[k] x) + sg[k] z
+ * in fp32 without contraction; where sg[k] == 0, z is neither drawn nor read. All tables are HOST arrays of length K
+ * (the fp32 casts of fp64 values: a = abar[tau[k]], p = abar[tau[k-1]] (1 at k = 0), a0 = 1/sqrt(a),
+ * b0 = sqrt(1/a - 1), sg = eta sqrt((1-p)/(1-a)) sqrt(1 - a/p), d = sqrt(1 - p - sg^2), c0 = sqrt(p) - d sqrt(a/(1-a)),
+ * cx = d/sqrt(1-a); row 0 is (c0, cx, sg) = (1, 0, 0)). w: the CFG weight. */
+typedef struct {
+  int32_t K;
+  const int32_t* tau;
+  const float* a0;
+  const float* b0;
+  const float* c0;
+  const float* cx;
+  const float* sg;
+  int32_t clip_x0;         /* 0 | 1 */
+  float w;
+} itsd_x0_schedule;
+
+/* Install an x0-form schedule: clears the step graphs, uploads the five tables, builds the time-embedding table as
+ * [K][sum Cout] rows for the timesteps tau, and sets T_sched = K ("sched_form" = 1). itsd_set_schedule puts the handle
+ * back into the ancestral form: the two calls replace each other. Under this schedule itsd_sampler_run's t_begin / t_end
+ * are ROWS, the step counter counts rows, the Philox stream id and the index into an injected noise [K][n][3][H][W] are
+ * the row, and itsd_sampler_predict_x0's t is a row (its time embedding is tau[row]'s; the caller passes tau[row]'s
+ * a0, b0). ITSD_ERR_INVALID with a message before any HIP call: a null struct or table, K < 1, tau negative or not
+ * strictly increasing, clip_x0 outside {0, 1}, a null handle, CFG with tau[K-1] >= the embedding table's rows. */
+int itsd_set_schedule_x0(itsd_unet* u, const itsd_x0_schedule* schedule);
+
 /* Run steps t_begin..t_end (inclusive, descending) of the ancestral sampler in
  * place on x[n,3,H,W]. With ITSD_RUN_GRAPH one denoising step is captured per
  * (n, x, labels, noise, option state) and replayed: seed, noise_offset and the clip
  * step are device-side run parameters, so rounds that differ only in them reuse it. noise == NULL: z ~ N(0,1) from counter-based Philox keyed
  * (seed, step, noise_offset + element); otherwise noise is [T][n][3][H][W] fp32 and
- * step t uses noise[t] (t >= 1; the reference draws no noise at t = 0). labels: CFG only. */
+ * step t uses noise[t] (t >= 1; the reference draws no noise at t = 0). labels: CFG only.
+ * Under an x0-form schedule (itsd_set_schedule_x0) the same call walks rows with that schedule's step; a graph
+ * captured under one form is never replayed under the other (the form is part of the cache key). */
 int itsd_sampler_run(itsd_unet* u, float* x, const int32_t* labels, int n, int t_begin, int t_end,
                      uint64_t seed, int64_t noise_offset, const float* noise, uint32_t flags, void* stream);
 
 /* x0[n,3,H,W] = clip(a0*x - b0*eps(x, t[, labels]), -1, 1): the sampler's own forward at step t
- * (guided for CFG) with the x0 epilogue; x is not modified. Needs itsd_set_schedule (t < T_sched).
+ * (guided for CFG) with the x0 epilogue; x is not modified. Needs itsd_set_schedule (t < T_sched) or
+ * itsd_set_schedule_x0 (t is then a row: the forward runs at timestep tau[t]).
  * x is the state x_t, the INPUT of step t (what itsd_sampler_run(.., t_end = t + 1) leaves); the caller passes
  * a0 = 1/sqrt(abar_t), b0 = sqrt(1/abar_t - 1) (fp64 on the host, cast). Runs eagerly: no step graph is captured or
  * evicted, and the NaN flag of the last itsd_sampler_run is left alone. ITSD_ERR_INVALID before any HIP call: null
@@ -218,7 +252,8 @@ int itsd_set_option(const char* key, int value);
 
 /* Introspection of a handle (no device work): "graph_captures" (step graphs captured and
  * instantiated so far; a search replays one graph across all its rounds), "max_batch",
- * "T_sched", "ws_bytes" (activation arena), "ops" (program length); and, synchronising the
+ * "T_sched" (timesteps, or the rows K of an x0-form schedule), "sched_form" (0 ancestral, 1 x0-form), "ws_bytes"
+ * (activation arena), "ops" (program length); and, synchronising the
  * handle's stream, "status" = the in-kernel hand-off status word of the last forward / sampler run
  * (0 ok; bit 0: attn_block_split_kernel's wait exhausted its bound, bit 1: conv3x3_gn_p5_kernel's shared split-K
  * combine -- ITSD_ERR_HANDOFF). */

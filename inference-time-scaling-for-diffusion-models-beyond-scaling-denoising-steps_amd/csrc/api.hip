@@ -163,7 +163,7 @@ struct Arena {
 // staged through handle-owned buffers and the seed, noise offset and clip step live in device
 // memory (RunParams), so every round of a search replays one graph.
 struct GraphEntry {
-  std::tuple<int, bool, const float*, int> key;
+  std::tuple<int, bool, const float*, int, int> key;  // (n, labels, noise, option generation, schedule form)
   hipGraphExec_t exec = nullptr;
 };
 
@@ -206,6 +206,11 @@ struct itsd_unet {
   float* coeff2 = nullptr;
   float* sqrt_var = nullptr;
   float* temb_table = nullptr;  // [T_sched][sumC]
+  // x0-form schedule (itsd_set_schedule_x0): sched_form 1, T_sched = its rows K, temb_table row k = timestep tau[k]'s,
+  // xrow = one allocation [5][K] (a0 | b0 | c0 | cx | sg); the three ancestral tables are then null, and the reverse
+  int sched_form = 0;
+  float* xrow = nullptr;
+  int clip_x0 = 0;
   float guide_w = 0.f, guide_w1 = 1.f;
   int* d_t = nullptr;
   int* d_nan = nullptr;
@@ -1314,6 +1319,17 @@ void clear_graphs(itsd_unet* u) {
   u->graphs.clear();
 }
 
+// Either schedule call starts here: no step graph and no table of the previous schedule, of either form, survives
+// (T_sched = 0 until the new one is complete, so a failed call leaves the handle without a schedule).
+void drop_schedule(itsd_unet* u) {
+  clear_graphs(u);
+  hipFree(u->coeff1); hipFree(u->coeff2); hipFree(u->sqrt_var); hipFree(u->xrow); hipFree(u->temb_table);
+  u->coeff1 = u->coeff2 = u->sqrt_var = u->xrow = u->temb_table = nullptr;
+  u->T_sched = 0;
+  u->sched_form = 0;
+  u->clip_x0 = 0;
+}
+
 int check_batch(itsd_unet* u, int n) {
   if (n <= 0 || n > u->d.max_batch)
     return fail(ITSD_ERR_INVALID, "batch " + std::to_string(n) + " outside [1, max_batch=" +
@@ -1361,11 +1377,11 @@ int leave_stream(itsd_unet* u, hipStream_t cs) {
   return ITSD_OK;
 }
 
-// The step graph of (n, labels present, noise pointer, option generation): the cached one, or one step of c (the
+// The step graph of (n, labels present, noise pointer, option generation, schedule form): the cached one, or one step of c (the
 // program, then the step counter's decrement) captured on u->stream, instantiated and cached -- 4 entries, the oldest
 // out. A failed capture is ended and its graph destroyed before the error is returned.
 int step_graph(itsd_unet* u, const RunCtx& c, int n, bool labels, const float* noise, hipGraphExec_t* exec) {
-  const auto key = std::make_tuple(n, labels, noise, itsd::g_option_gen);
+  const auto key = std::make_tuple(n, labels, noise, itsd::g_option_gen, u->sched_form);
   for (auto& g : u->graphs)
     if (g.key == key) { *exec = g.exec; return ITSD_OK; }
   hipStream_t s = u->stream;
@@ -1578,6 +1594,7 @@ int itsd_unet_query(const itsd_unet* u, const char* key, int64_t* value) {
   if (!std::strcmp(key, "graph_captures")) *value = u->graph_captures;
   else if (!std::strcmp(key, "max_batch")) *value = u->d.max_batch;
   else if (!std::strcmp(key, "T_sched")) *value = u->T_sched;
+  else if (!std::strcmp(key, "sched_form")) *value = u->sched_form;
   else if (!std::strcmp(key, "ws_bytes")) *value = (int64_t)u->ws_bytes;
   else if (!std::strcmp(key, "ops")) *value = (int64_t)u->ops.size();
   else if (!std::strcmp(key, "status")) {  // synchronous: the in-kernel hand-off status word of the last forward / run
@@ -1649,7 +1666,7 @@ int itsd_unet_destroy(itsd_unet* u) {
   clear_graphs(u);
   hipFree(u->wdev); hipFree(u->ws); hipFree(u->emb_buf); hipFree(u->h1_buf); hipFree(u->te_buf);
   hipFree(u->proj_buf); hipFree(u->cemb_table); hipFree(u->coeff1); hipFree(u->coeff2); hipFree(u->sqrt_var);
-  hipFree(u->temb_table); hipFree(u->d_t); hipFree(u->d_nan); hipFree(u->d_run); hipFree(u->x_state); hipFree(u->lab_state); hipFree(u->zero_page);
+  hipFree(u->xrow); hipFree(u->temb_table); hipFree(u->d_t); hipFree(u->d_nan); hipFree(u->d_run); hipFree(u->x_state); hipFree(u->lab_state); hipFree(u->zero_page);
   hipFree(u->splitk_ws);
   hipFree(u->tickets);
   hipFree(u->attn_sync);
@@ -1695,9 +1712,7 @@ int itsd_set_schedule(itsd_unet* u, int T, const float* coeff1, const float* coe
   if (u->cfg && T > u->d.T)
     return fail(ITSD_ERR_INVALID, "CFG time-embedding table has " + std::to_string(u->d.T) + " rows < sampler T");
   HIPCHK(hipSetDevice(u->device));
-  clear_graphs(u);
-  hipFree(u->coeff1); hipFree(u->coeff2); hipFree(u->sqrt_var); hipFree(u->temb_table);
-  u->coeff1 = u->coeff2 = u->sqrt_var = u->temb_table = nullptr;
+  drop_schedule(u);
   HIPCHK(hipMalloc(&u->coeff1, T * 4));
   HIPCHK(hipMalloc(&u->coeff2, T * 4));
   HIPCHK(hipMalloc(&u->sqrt_var, T * 4));
@@ -1711,6 +1726,47 @@ int itsd_set_schedule(itsd_unet* u, int T, const float* coeff1, const float* coe
   u->T_sched = T;
   u->guide_w = w;
   u->guide_w1 = (float)(1.0 + (double)w);
+  return ITSD_OK;
+}
+
+// The x0-form schedule: K rows, row k run at timestep tau[k]. The time-embedding table is built for tau (temb_rows with
+// a device copy of it), so everything downstream -- the step program, itsd_sampler_predict_x0 -- indexes by row.
+int itsd_set_schedule_x0(itsd_unet* u, const itsd_x0_schedule* sc) {
+  if (!sc) return fail(ITSD_ERR_INVALID, "itsd_set_schedule_x0: null schedule");
+  if (!sc->tau || !sc->a0 || !sc->b0 || !sc->c0 || !sc->cx || !sc->sg)
+    return fail(ITSD_ERR_INVALID, "itsd_set_schedule_x0: null table");
+  const int K = sc->K;
+  if (K < 1) return fail(ITSD_ERR_INVALID, "itsd_set_schedule_x0: K = " + std::to_string(K) + " < 1");
+  for (int k = 0; k < K; ++k)
+    if (sc->tau[k] < 0 || (k && sc->tau[k] <= sc->tau[k - 1]))
+      return fail(ITSD_ERR_INVALID, "itsd_set_schedule_x0: tau[" + std::to_string(k) + "] = " +
+                                        std::to_string(sc->tau[k]) + ": timesteps must be >= 0 and strictly increasing");
+  if (sc->clip_x0 != 0 && sc->clip_x0 != 1)
+    return fail(ITSD_ERR_INVALID, "itsd_set_schedule_x0: clip_x0 = " + std::to_string(sc->clip_x0) + " is neither 0 nor 1");
+  if (!u) return fail(ITSD_ERR_INVALID, "itsd_set_schedule_x0: null handle");
+  if (u->cfg && sc->tau[K - 1] >= u->d.T)
+    return fail(ITSD_ERR_INVALID, "CFG time-embedding table has " + std::to_string(u->d.T) + " rows <= timestep " +
+                                      std::to_string(sc->tau[K - 1]));
+  HIPCHK(hipSetDevice(u->device));
+  drop_schedule(u);
+  HIPCHK(hipMalloc(&u->xrow, (size_t)5 * K * 4));
+  const float* rows[5] = {sc->a0, sc->b0, sc->c0, sc->cx, sc->sg};
+  for (int i = 0; i < 5; ++i) HIPCHK(hipMemcpy(u->xrow + (size_t)i * K, rows[i], (size_t)K * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMalloc(&u->temb_table, (size_t)K * u->sumC * 4));
+  CHK(alloc_rows(u, K));
+  int* d_tau = nullptr;
+  HIPCHK(hipMalloc(&d_tau, (size_t)K * 4));
+  int rc = ITSD_OK;
+  if (hipMemcpy(d_tau, sc->tau, (size_t)K * 4, hipMemcpyHostToDevice) != hipSuccess) rc = fail(ITSD_ERR_HIP, "tau upload");
+  if (rc == ITSD_OK) rc = temb_rows(u, d_tau, K, 0, false, u->temb_table, u->stream);
+  if (rc == ITSD_OK && hipStreamSynchronize(u->stream) != hipSuccess) rc = fail(ITSD_ERR_HIP, "temb rows");
+  hipFree(d_tau);
+  if (rc != ITSD_OK) return rc;
+  u->T_sched = K;
+  u->sched_form = 1;
+  u->clip_x0 = sc->clip_x0;
+  u->guide_w = sc->w;
+  u->guide_w1 = (float)(1.0 + (double)sc->w);
   return ITSD_OK;
 }
 
@@ -1732,8 +1788,12 @@ int itsd_sampler_run(itsd_unet* u, float* x, const int32_t* labels, int n, int t
 
   RunCtx c = step_ctx(u, n, u->x_state, labels ? u->lab_state : nullptr);
   TailArgs& t = c.tail;
-  t.step_mode = 1; t.tsel = u->d_t;
+  t.step_mode = u->sched_form ? 3 : 1; t.tsel = u->d_t;
   t.coeff1 = u->coeff1; t.coeff2 = u->coeff2; t.sqrt_var = u->sqrt_var;
+  if (u->sched_form) {  // rows, not timesteps: d_t, the Philox stream id and the injected-noise index are the row
+    for (int i = 0; i < 5; ++i) t.xrow[i] = u->xrow + (size_t)i * u->T_sched;
+    t.clip_x0 = u->clip_x0;
+  }
   t.noise = noise; t.run = u->d_run; t.nan_flag = u->d_nan;
 
   RunParams rp{};

@@ -317,7 +317,8 @@ struct TailArgs {
   float guide_w;        // w (fp32 cast of the Python float)
   float guide_w1;       // (1 + w) computed in double then cast, as the reference's scalar
   // mode
-  int step_mode;        // 0: write eps NCHW; 1: sampler update of x in place; 2: x0_out = clip(a0 x - b0 eps) (x read only)
+  int step_mode;        // 0: write eps NCHW; 1: sampler update of x in place; 2: x0_out = clip(a0 x - b0 eps) (x read only);
+                        // 3: the x0-form update of x in place (rows of xrow, below)
   float* eps_out;       // NCHW [n][3][H][W]
   float* x;             // NCHW [n][3][H][W]
   const int* tsel;      // current step t (device)
@@ -334,6 +335,11 @@ struct TailArgs {
   // step_mode 2 (itsd_sampler_predict_x0): a0 = 1/sqrt(abar_t), b0 = sqrt(1/abar_t - 1) as fp32, output NCHW [n][3][H][W]
   float a0, b0;
   float* x0_out;
+  // step_mode 3 (itsd_sampler_run under an x0-form schedule, itsd_set_schedule_x0): row k = *tsel of five device
+  // tables [K] -- a0, b0, c0, cx, sg in this order -- and whether the x_0 estimate is clipped. tsel, noise (indexed by
+  // row), run and nan_flag as in step_mode 1; coeff1 / coeff2 / sqrt_var are not read
+  const float* xrow[5];
+  int clip_x0;
 };
 
 constexpr int kBranchChunk = 256;  // parent-table rows a branch_kernel launch carries in its arguments (1 KiB)

@@ -1456,7 +1456,7 @@ __device__ __forceinline__ float philox_normal(unsigned long long seed, unsigned
 // ============================================================================ tail conv + sampler step
 // tail = GN -> Swish -> Conv2d(C, 3, 3, padding=1) (Model.py:252-256, 282). The GN+Swish
 // output g is produced by groupnorm_kernel (tail_mfma_kernel applies it itself); the three kernels below do the
-// 3-output conv per pixel and hand each output element's eps to tail_finish, which ends in one of three ways:
+// 3-output conv per pixel and hand each output element's eps to tail_finish, which ends in one of four ways:
 //   eps  (TailArgs::step_mode 0, the forward API)  eps_out = eps
 //   step (step_mode 1)  the ancestral update of Diffusion.py:67-71,96-100 in place on x:
 //          mean = coeff1[t]*x - coeff2[t]*eps ;  x = mean + sqrt(var[t]) * z  (z = 0 at t = 0; injected or Philox),
@@ -1465,42 +1465,59 @@ __device__ __forceinline__ float philox_normal(unsigned long long seed, unsigned
 //   x0   (step_mode 2, its own instantiation: the eps / step kernels' code is what it was)
 //          x0_out = clip(a0 * x - b0 * eps, -1, 1)   (the x_0 estimate of the state x at this step)
 //          x is only read, no noise is drawn, the NaN flag is not touched, a.run and the schedule tables are not read.
+//   x0 step (step_mode 3, its own instantiation as well)  DDIM(eta) through the x_0 estimate, in place on x, with the
+//          scalars of row k = *tsel of the five TailArgs::xrow tables:
+//          x0 = a0*x - b0*eps, clipped to [-1, 1] iff clip_x0 ;  m = (c0*x0) + (cx*x) ;  x = sg != 0 ? m + sg*z : m
+//          (no contraction: the tests demand these bits). z is noise[k] or Philox (seed, k, noise_offset + o); where
+//          sg == 0 it is neither drawn nor read (wave-uniform: one row a launch). NaN test, clip_at clip and the
+//          flag as in the ancestral step.
 // CFG: eps = (1+w) eps_c - w eps_u (DiffusionCondition.py:85) with the unconditional
-// branch at image index img + n of g (guided before tail_finish, in all three modes).
+// branch at image index img + n of g (guided before tail_finish, in all four modes).
+// EPI, the kernels' template parameter, names the instantiation: 0 eps / step, 1 x0, 2 x0 step.
 __device__ __forceinline__ float tail_x0(float a0, float b0, float xv, float e) {
 #pragma clang fp contract(off)
   const float v = a0 * xv - b0 * e;
   return fminf(fmaxf(v, -1.0f), 1.0f);
 }
 
-// The step's scalars: row t of the schedule tables and the run's parameters. Loaded in step mode only; the other two
-// modes read none of them.
+// The step's scalars: row t of the schedule tables and the run's parameters. Loaded in the two step modes only (the
+// x0 step: c1, c2, sv hold the row's c0, cx, sg, and a0, b0 its x_0 coefficients); the other two modes read none of
+// them.
 struct TailStep {
   int t = 0;
   float c1 = 0.f, c2 = 0.f, sv = 0.f;
   unsigned long long seed = 0;
   long long noise_offset = 0;
   int clip_at = -1;
+  float a0 = 0.f, b0 = 0.f;
 };
-template <bool X0>
+template <int EPI>
 __device__ __forceinline__ TailStep tail_step_load(const TailArgs& a) {
   TailStep s;
-  if (!X0 && a.step_mode) {
+  if (EPI == 2 || (EPI == 0 && a.step_mode)) {
     s.t = *a.tsel;
     s.seed = a.run->seed;
     s.noise_offset = a.run->noise_offset;
     s.clip_at = a.run->clip_at;
-    s.c1 = a.coeff1[s.t];
-    s.c2 = a.coeff2[s.t];
-    s.sv = a.sqrt_var[s.t];
+    if constexpr (EPI == 2) {
+      s.a0 = a.xrow[0][s.t];
+      s.b0 = a.xrow[1][s.t];
+      s.c1 = a.xrow[2][s.t];
+      s.c2 = a.xrow[3][s.t];
+      s.sv = a.xrow[4][s.t];
+    } else {
+      s.c1 = a.coeff1[s.t];
+      s.c2 = a.coeff2[s.t];
+      s.sv = a.sqrt_var[s.t];
+    }
   }
   return s;
 }
 
 // x at NCHW offset o where the epilogue reads it (the eps mode has no x)
-template <bool X0>
+template <int EPI>
 __device__ __forceinline__ float tail_x(const TailArgs& a, size_t o) {
-  return (X0 || a.step_mode) ? a.x[o] : 0.f;
+  return (EPI || a.step_mode) ? a.x[o] : 0.f;
 }
 
 // NCHW offset of output channel oc at pixel opx of a block of full rows that starts at row y0 of image img
@@ -1511,12 +1528,26 @@ __device__ __forceinline__ size_t tail_offset(int img, int y0, int opx, int oc, 
 
 // One output element: its (guided) eps e, its NCHW offset o, its x value xv (tail_x) and the step's scalars. Returns
 // whether the step's new x is NaN (false in the other two modes).
-template <bool X0>
+template <int EPI>
 __device__ __forceinline__ bool tail_finish(const TailArgs& a, const TailStep& s, size_t o, float xv, float e) {
 #pragma clang fp contract(off)
-  if constexpr (X0) {
+  if constexpr (EPI == 1) {
     a.x0_out[o] = tail_x0(a.a0, a.b0, xv, e);
     return false;
+  }
+  if constexpr (EPI == 2) {
+    float x0 = s.a0 * xv - s.b0 * e;
+    if (a.clip_x0) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    float xn = (s.c1 * x0) + (s.c2 * xv);
+    if (s.sv != 0.f) {  // (one row a launch: uniform)
+      const float z = a.noise ? a.noise[(size_t)s.t * a.n * 3 * (a.H * a.W) + o]
+                              : philox_normal(s.seed, (unsigned)s.t, (unsigned long long)(s.noise_offset + (long long)o));
+      xn = xn + s.sv * z;
+    }
+    const bool bad = xn != xn;
+    if (s.t == s.clip_at) xn = fminf(fmaxf(xn, -1.0f), 1.0f);
+    a.x[o] = xn;
+    return bad;
   }
   if (!a.step_mode) {
     a.eps_out[o] = e;
@@ -1545,7 +1576,7 @@ __device__ __forceinline__ void tail_stage_weights(float* wl, const float* w, in
   }
 }
 
-template <typename T, bool X0 = false>
+template <typename T, int EPI = 0>
 __global__ __launch_bounds__(256) void tail_kernel(TailArgs a) {
   constexpr int EPC = 16 / (int)sizeof(T);
   extern __shared__ __attribute__((aligned(16))) float wl[];  // [9][C][3]
@@ -1594,12 +1625,12 @@ __global__ __launch_bounds__(256) void tail_kernel(TailArgs a) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) eps[c] = w1 * eps[c] - a.guide_w * u[c];
   }
-  const TailStep st = tail_step_load<X0>(a);
+  const TailStep st = tail_step_load<EPI>(a);
   bool bad = false;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     const size_t o = ((size_t)img * 3 + c) * HW + rem;
-    bad |= tail_finish<X0>(a, st, o, tail_x<X0>(a, o), eps[c]);
+    bad |= tail_finish<EPI>(a, st, o, tail_x<EPI>(a, o), eps[c]);
   }
   if (bad) atomicOr(a.nan_flag, 1);
 }
@@ -1607,7 +1638,7 @@ __global__ __launch_bounds__(256) void tail_kernel(TailArgs a) {
 // Tiled tail: one block per 64 output pixels (64/W full rows of one image); the input
 // halo rows are staged once in LDS (coalesced 16-B loads, padded pixel stride: no bank
 // conflicts) and 4 threads per pixel split the channels, reduced by lane shuffles.
-template <typename T, bool X0 = false>
+template <typename T, int EPI = 0>
 __global__ __launch_bounds__(256) void tail2_kernel(TailArgs a) {
   constexpr int EPC = 16 / (int)sizeof(T);
   extern __shared__ __attribute__((aligned(16))) char tsm[];
@@ -1682,7 +1713,7 @@ __global__ __launch_bounds__(256) void tail2_kernel(TailArgs a) {
     e = a.guide_w1 * e - a.guide_w * u;
   }
   const size_t o = tail_offset(img, y0, opx, oc, H, W);
-  if (tail_finish<X0>(a, tail_step_load<X0>(a), o, tail_x<X0>(a, o), e)) atomicOr(a.nan_flag, 1);
+  if (tail_finish<EPI>(a, tail_step_load<EPI>(a), o, tail_x<EPI>(a, o), e)) atomicOr(a.nan_flag, 1);
 }
 
 // bf16 tail on MFMA with the tail GroupNorm+SiLU fused (Model.py:252-256 / 282, then the
@@ -1705,7 +1736,7 @@ __global__ __launch_bounds__(256) void tail2_kernel(TailArgs a) {
 #endif
 __host__ __device__ constexpr int tail_pst(int C) { return 2 * C + (ITSD_TAIL_PAD32 ? 32 : 16); }
 
-template <int TM_PX, int NTH, bool X0 = false>
+template <int TM_PX, int NTH, int EPI = 0>
 __global__ __launch_bounds__(NTH, 2) void tail_mfma_kernel(TailArgs a) {
   constexpr int NW = NTH / 64, GPW = TM_PX / 16 / NW;  // waves; 16-pixel MFMA groups a wave
   static_assert(GPW >= 1 && GPW * 16 * NW == TM_PX, "tail geometry");
@@ -1732,8 +1763,8 @@ __global__ __launch_bounds__(NTH, 2) void tail_mfma_kernel(TailArgs a) {
   constexpr int TIT = (TM_PX * 3 + NTH - 1) / NTH;
   float xpre[TIT] = {};
   TailStep st;
-  if (X0 || a.step_mode) {
-    st = tail_step_load<X0>(a);
+  if (EPI || a.step_mode) {
+    st = tail_step_load<EPI>(a);
 #pragma unroll
     for (int k = 0; k < TIT; ++k) {
       const int it = tid + NTH * k, opx = it < TM_PX * 3 ? it / 3 : 0, oc = it < TM_PX * 3 ? it - opx * 3 : 0;
@@ -1834,7 +1865,7 @@ __global__ __launch_bounds__(NTH, 2) void tail_mfma_kernel(TailArgs a) {
       const float u = red[(TM_PX + opx) * 3 + oc] + a.b[oc];
       e = a.guide_w1 * e - a.guide_w * u;
     }
-    if (tail_finish<X0>(a, st, tail_offset(img, y0, opx, oc, H, W), xpre[k], e)) atomicOr(a.nan_flag, 1);
+    if (tail_finish<EPI>(a, st, tail_offset(img, y0, opx, oc, H, W), xpre[k], e)) atomicOr(a.nan_flag, 1);
   }
 }
 
@@ -1851,23 +1882,32 @@ static bool tail_mfma_ok_px(int px, int H, int W, int C) {
 size_t tail_mfma_smem(int H, int W, int C) { return tail_mfma_smem_px(128, H, W, C); }
 bool tail_mfma_ok(int H, int W, int C) { return tail_mfma_ok_px(128, H, W, C); }
 
-// step_mode 2 needs its operands (and nothing of the step's)
-static bool tail_x0_ok(const TailArgs& a) { return a.step_mode != 2 || (a.x && a.x0_out); }
+// step_mode 2 needs its operands (and nothing of the step's); step_mode 3 its tables and the step's run state
+static bool tail_x0_ok(const TailArgs& a) {
+  if (a.step_mode == 3) {
+    for (const float* p : a.xrow)
+      if (!p) return false;
+    return a.x && a.tsel && a.run && a.nan_flag && (a.clip_x0 == 0 || a.clip_x0 == 1);
+  }
+  return a.step_mode != 2 || (a.x && a.x0_out);
+}
 
 // The body of a tail launcher from its launch geometry on: launches the instantiation a.step_mode selects (X0K for the
-// x0 epilogue, PLAIN for eps and step; each under its own name, which the census and the profiles key on) and returns
-// the launch's status. BIG: the pair may use up to kTailSmemMax of dynamic shared memory; the attribute is set once.
-#define ITSD_RETURN_TAIL_LAUNCH(PLAIN, X0K, BIG, grid, block, sm, s, a)                                        \
+// x0 epilogue, XSK for the x0-form step, PLAIN for eps and step; each under its own name, which the census and the
+// profiles key on) and returns the launch's status. BIG: the three may use up to kTailSmemMax of dynamic shared
+// memory; the attribute is set once.
+#define ITSD_RETURN_TAIL_LAUNCH(PLAIN, X0K, XSK, BIG, grid, block, sm, s, a)                                   \
   do {                                                                                                         \
     static bool attr = !(BIG);                                                                                 \
     if (!attr) {                                                                                               \
-      for (const void* f : {(const void*)PLAIN, (const void*)X0K}) {                                           \
+      for (const void* f : {(const void*)PLAIN, (const void*)X0K, (const void*)XSK}) {                         \
         hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTailSmemMax);  \
         if (e != hipSuccess) return e;                                                                         \
       }                                                                                                        \
       attr = true;                                                                                             \
     }                                                                                                          \
     if ((a).step_mode == 2) ITSD_LAUNCH(X0K, grid, block, sm, s, a);                                           \
+    else if ((a).step_mode == 3) ITSD_LAUNCH(XSK, grid, block, sm, s, a);                                      \
     else ITSD_LAUNCH(PLAIN, grid, block, sm, s, a);                                                            \
     return hipGetLastError();                                                                                  \
   } while (0)
@@ -1876,8 +1916,8 @@ hipError_t launch_tail_mfma(const TailArgs& a, hipStream_t s) {
   if (!a.coef || !a.wmf || !tail_mfma_ok(a.H, a.W, a.C) || !tail_x0_ok(a)) return hipErrorInvalidValue;
   const dim3 grid(a.n * (a.H / (128 / a.W)));
   const size_t sm = tail_mfma_smem_px(128, a.H, a.W, a.C);
-  ITSD_RETURN_TAIL_LAUNCH((tail_mfma_kernel<128, 512>), (tail_mfma_kernel<128, 512, true>), true, grid, dim3(512), sm,
-                          s, a);
+  ITSD_RETURN_TAIL_LAUNCH((tail_mfma_kernel<128, 512>), (tail_mfma_kernel<128, 512, 1>), (tail_mfma_kernel<128, 512, 2>),
+                          true, grid, dim3(512), sm, s, a);
 }
 
 template <typename T>
@@ -1887,12 +1927,13 @@ hipError_t launch_tail(const TailArgs& a, hipStream_t s) {
     const size_t sm = 27 * a.C * 4 + (size_t)(64 / a.W + 2) * (a.W + 2) * (a.C * sizeof(T) + 16) + 2 * 4 * 64 * 3 * 4;
     if (sm > kTailSmemMax) return hipErrorInvalidValue;
     const dim3 grid(a.n * (a.H / (64 / a.W)));
-    ITSD_RETURN_TAIL_LAUNCH(tail2_kernel<T>, (tail2_kernel<T, true>), true, grid, dim3(256), sm, s, a);
+    ITSD_RETURN_TAIL_LAUNCH(tail2_kernel<T>, (tail2_kernel<T, 1>), (tail2_kernel<T, 2>), true, grid, dim3(256), sm, s,
+                            a);
   }
   const long long total = (long long)a.n * a.H * a.W;
   const dim3 grid((unsigned)((total + 255) / 256));
-  ITSD_RETURN_TAIL_LAUNCH(tail_kernel<T>, (tail_kernel<T, true>), false, grid, dim3(256), 27 * a.C * sizeof(float), s,
-                          a);
+  ITSD_RETURN_TAIL_LAUNCH(tail_kernel<T>, (tail_kernel<T, 1>), (tail_kernel<T, 2>), false, grid, dim3(256),
+                          27 * a.C * sizeof(float), s, a);
 }
 template hipError_t launch_tail<float>(const TailArgs&, hipStream_t);
 template hipError_t launch_tail<bf16_t>(const TailArgs&, hipStream_t);

@@ -1,4 +1,5 @@
-"""Ancestral samplers with the reference interface.
+"""Samplers with the reference interface: the reference's ancestral sampler (the default, and the parity contract) and
+an opt-in few-step one.
 
 * ``GaussianDiffusionSampler``     <- ``Diffusion/Diffusion.py:50-102``
 * ``CondGaussianDiffusionSampler`` <- ``DiffusionFreeGuidence/DiffusionCondition.py:56-105``
@@ -13,14 +14,20 @@ RNG: the reference draws ``torch.randn_like`` from the global generator each ste
 Here the per-run Philox seed is drawn from the global torch generator, so runs
 are deterministic under ``torch.manual_seed``; bit-identical noise to the reference
 is available by passing ``noise=`` (see ``reference_noise_plan``).
+
+``sampler="ddim"`` (no reference counterpart) walks K <= T *rows*: row k evaluates the model at timestep tau[k]
+(``schedule.strided_timesteps`` or an explicit list) and steps by DDIM(eta) written through the x_0 estimate, clipped to
+[-1, 1] under ``clip_x0`` (``schedule.x0_form_rows``, ``itsd_set_schedule_x0``). Every step argument of ``run`` and
+``predict_x0``, the injected-noise index and the Philox stream id are then rows; ``n_steps`` is K.
 """
 from __future__ import annotations
 
+import numbers
 from typing import Optional, Sequence, Tuple
 
 import torch
 
-from .schedule import make_schedule, x0_coeffs
+from .schedule import check_timesteps, make_schedule, strided_timesteps, x0_coeffs, x0_form_rows
 
 
 def _extract(v: torch.Tensor, t: torch.Tensor, ndim: int) -> torch.Tensor:
@@ -34,18 +41,47 @@ def _draw_seed() -> int:
 
 
 class GaussianDiffusionSampler:
-    def __init__(self, model, beta_1: float, beta_T: float, T: int, w: float = 0.0):
+    def __init__(self, model, beta_1: float, beta_T: float, T: int, w: float = 0.0, *, sampler: str = "ddpm",
+                 steps=None, eta: float = 0.0, clip_x0: bool = False):
         self.model = model
         self.T = int(T)
         self.w = float(w)
         self.sched = make_schedule(beta_1, beta_T, T)
+        if sampler not in ("ddpm", "ddim"):
+            raise ValueError(f"sampler must be 'ddpm' or 'ddim', not {sampler!r}")
+        self.sampler = sampler
         # the reference's registered buffers (Diffusion.py:57-65)
         self.betas = self.sched.betas
         self.coeff1 = self.sched.coeff1
         self.coeff2 = self.sched.coeff2
         self.posterior_var = self.sched.posterior_var
         self._sched_args = (self.sched.coeff1_f32, self.sched.coeff2_f32, self.sched.sqrt_var_f32, self.w)
+        self.tau = list(range(self.T))  # row -> timestep (the identity for ddpm)
+        if sampler == "ddim":
+            if not 0.0 <= float(eta) <= 1.0:
+                raise ValueError(f"eta = {eta} outside [0, 1]")
+            if steps is None or isinstance(steps, numbers.Integral):
+                self.tau = strided_timesteps(self.T, self.T if steps is None else steps)
+            else:
+                self.tau = check_timesteps(steps, self.T)
+            self.eta, self.clip_x0 = float(eta), bool(clip_x0)
+            self.rows = x0_form_rows(self.sched.alphas_bar, self.tau, self.eta)
+            self._sched_args = (self.tau, self.rows, self.clip_x0, self.w)
+        elif steps is not None or eta != 0.0 or clip_x0:
+            raise ValueError("steps, eta and clip_x0 belong to sampler='ddim'")
         self.last_seed = None  # Philox key of the last run (set by run)
+
+    @property
+    def n_steps(self) -> int:
+        """Rows a full run walks: T for ddpm, K for ddim."""
+        return len(self.tau)
+
+    @property
+    def abar_rows(self) -> torch.Tensor:
+        """alphas_bar by row (fp64): abar[tau] for ddim, ``sched.alphas_bar`` itself for ddpm."""
+        if self.sampler == "ddpm":
+            return self.sched.alphas_bar
+        return self.sched.alphas_bar[torch.tensor(self.tau, dtype=torch.long)]
 
     def to(self, *args, **kwargs):
         if args or "device" in kwargs:
@@ -58,7 +94,7 @@ class GaussianDiffusionSampler:
     def _native(self, n: int):
         nat = self.model.native(n)
         if getattr(nat, "_sched_args", None) is not self._sched_args:
-            nat.set_schedule(*self._sched_args)
+            (nat.set_schedule_x0 if self.sampler == "ddim" else nat.set_schedule)(*self._sched_args)
             nat._sched_args = self._sched_args
         return nat
 
@@ -81,8 +117,9 @@ class GaussianDiffusionSampler:
     def run(self, x: torch.Tensor, t_begin: Optional[int] = None, t_end: int = 0, labels=None, seed=None,
             noise: Optional[torch.Tensor] = None, noise_offset: int = 0, graph: bool = True, clip=None,
             sync: bool = True) -> torch.Tensor:
-        """In-place steps t_begin..t_end on a contiguous fp32 device tensor x."""
-        t_begin = self.T - 1 if t_begin is None else int(t_begin)
+        """In-place steps t_begin..t_end on a contiguous fp32 device tensor x (rows of the schedule: timesteps for
+        ddpm)."""
+        t_begin = self.n_steps - 1 if t_begin is None else int(t_begin)
         if clip is None:
             clip = t_end == 0
         if seed is None and noise is None:
@@ -103,14 +140,14 @@ class GaussianDiffusionSampler:
         """The x_0 estimate of a half-denoised state: x is x_t, the input of step t (what ``run(.., t_end=t + 1)``
         leaves); returns clip(x / sqrt(abar_t) - sqrt(1/abar_t - 1) eps(x, t), -1, 1) as a new tensor, with the eps
         the sampler's step t would use (guided for the conditional sampler, which needs ``labels``). x is not
-        modified (``itsd_sampler_predict_x0``)."""
+        modified (``itsd_sampler_predict_x0``). t is a row: under ddim the timestep is tau[t]."""
         t = int(t)
-        if not 0 <= t < self.T:
-            raise ValueError(f"step {t} outside [0, T={self.T})")
+        if not 0 <= t < self.n_steps:
+            raise ValueError(f"step {t} outside [0, {self.n_steps})")
         x = x.to(self.model.device, torch.float32).contiguous()
         if labels is not None:
             labels = labels.flatten().to(x.device, torch.int32).contiguous()
-        a0, b0 = x0_coeffs(self.sched.alphas_bar, t)
+        a0, b0 = x0_coeffs(self.sched.alphas_bar, self.tau[t])
         out = torch.empty_like(x)
         self._native(x.shape[0]).predict_x0(x, t, a0, b0, out, labels=labels)
         return out
@@ -126,6 +163,8 @@ class GaussianDiffusionSampler:
     def reference_noise(self, shape: Sequence[int]) -> torch.Tensor:
         """The T-1 draws one reference sampler call takes from the global CPU generator
         (``Diffusion.py:94-96``: ``randn_like`` at t = T-1 .. 1), as [T, *shape] by step t."""
+        if self.sampler != "ddpm":
+            raise ValueError("the reference has no few-step sampler: there is no reference draw order under ddim")
         z = [torch.randn(tuple(shape)) for _ in range(self.T - 1)]
         return torch.stack(z + [torch.zeros(tuple(shape))]).flip(0)
 
@@ -134,6 +173,9 @@ class GaussianDiffusionSampler:
         (``search_algorithm.py:71``). reference_rng: each call consumes the reference's
         per-step draws from the global generator (bit-identical candidates to the reference
         loop under ``torch.manual_seed``); otherwise Philox seeded from that generator."""
+
+        if reference_rng and self.sampler != "ddpm":
+            raise ValueError("reference_rng=True needs sampler='ddpm': the reference has no draw order for ddim")
 
         def fn(noise: torch.Tensor, show_progress: bool = False, **kw) -> torch.Tensor:
             z = self.reference_noise(noise.shape) if reference_rng else None
@@ -146,8 +188,8 @@ class GaussianDiffusionSampler:
 class CondGaussianDiffusionSampler(GaussianDiffusionSampler):
     """``DiffusionCondition.py:56``: guided eps = (1+w) eps(x,t,y) - w eps(x,t,0)."""
 
-    def __init__(self, model, beta_1: float, beta_T: float, T: int, w: float = 0.0):
-        super().__init__(model, beta_1, beta_T, T, w)
+    def __init__(self, model, beta_1: float, beta_T: float, T: int, w: float = 0.0, **kw):
+        super().__init__(model, beta_1, beta_T, T, w, **kw)
 
     def forward(self, x_T: torch.Tensor, labels: torch.Tensor, noise: Optional[torch.Tensor] = None,
                 seed: Optional[int] = None, graph: bool = True) -> torch.Tensor:

@@ -33,6 +33,18 @@ Keys beyond the reference (all optional):
         verifier: oracle         # oracle | selfsup | aesthetic
         bestImgName: SearchBestImgs.png
 
+* ``sampler``: a block selecting the sampler of the eval AND of the ``search`` block's rounds (no reference
+  counterpart: the reference has the ancestral sampler only). Absent, or ``kind: ddpm``: the ancestral sampler::
+
+      sampler:
+        kind: ddim               # ddpm | ddim
+        steps: 50                # rows K in [1, inference T] (default: T); strided over the T timesteps
+        eta: 0.0                 # in [0, 1]: 0 deterministic, 1 the ancestral variance
+        clip_x0: true            # clip the x_0 estimate inside every step (bounded trajectories)
+
+  Under ddim the search block's ``injection_step`` / ``renoise_steps`` count rows. ``sampler.steps=20`` overrides work
+  as for ``search.*``.
+
 There is no training entry: ``state: train`` raises (training is out of scope).
 """
 from __future__ import annotations
@@ -385,6 +397,35 @@ def _rank_world() -> Tuple[int, int]:
     return 0, 1
 
 
+def sampler_kwargs(cfg: Dict[str, Any], T: int) -> Dict[str, Any]:
+    """The ``sampler:`` block as the sampler classes' keyword arguments ({} for the ancestral default). Every bad value
+    raises a ValueError that names its key."""
+    s = cfg.get("sampler")
+    if s is None:
+        return {}
+    if not isinstance(s, dict):
+        raise ValueError("sampler must be a block (kind / steps / eta / clip_x0)")
+    unknown = set(s) - {"kind", "steps", "eta", "clip_x0"}
+    if unknown:
+        raise ValueError(f"unknown sampler keys {sorted(unknown)} (kind | steps | eta | clip_x0)")
+    kind = s.get("kind", "ddpm")
+    kind = kind.lower() if isinstance(kind, str) else kind
+    if kind not in ("ddpm", "ddim"):
+        raise ValueError(f"unknown sampler.kind '{kind}' (ddpm | ddim)")
+    steps, eta, clip = s.get("steps"), s.get("eta", 0.0), s.get("clip_x0", False)
+    if steps is not None and (isinstance(steps, bool) or not isinstance(steps, int) or not 1 <= steps <= int(T)):
+        raise ValueError(f"sampler.steps = {steps!r} must be an integer in [1, inference T = {int(T)}]")
+    if isinstance(eta, bool) or not isinstance(eta, (int, float)) or not 0.0 <= eta <= 1.0:
+        raise ValueError(f"sampler.eta = {eta!r} must be a number in [0, 1]")
+    if not isinstance(clip, bool):
+        raise ValueError(f"sampler.clip_x0 = {clip!r} must be true or false")
+    if kind == "ddpm":
+        if steps not in (None, int(T)) or eta != 0.0 or clip:
+            raise ValueError("sampler.steps / eta / clip_x0 need sampler.kind: ddim")
+        return {}
+    return {"sampler": "ddim", "steps": steps, "eta": float(eta), "clip_x0": clip}
+
+
 def _search(cfg: Dict[str, Any], sampler, img_size: int, labels: Optional[torch.Tensor]) -> Optional[Dict[str, Any]]:
     s = cfg.get("search") or {}
     algo = (s.get("algorithm") or "none").lower()
@@ -492,7 +533,8 @@ def eval(cfg: Dict[str, Any]) -> Dict[str, Any]:  # noqa: A001 (reference name)
             print(f"Using inference T={inference_T} (model was trained with T={cfg['T']})")
         else:
             print(f"Using same T={cfg['T']} for inference")
-        sampler = GaussianDiffusionSampler(model, cfg["beta_1"], cfg["beta_T"], inference_T)
+        sampler = GaussianDiffusionSampler(model, cfg["beta_1"], cfg["beta_T"], inference_T,
+                                           **sampler_kwargs(cfg, inference_T))
         img_size = int(cfg.get("img_size") or 256)
         noisy = torch.randn(size=[cfg["batch_size"], 3, img_size, img_size], device=model.device)
         imgs = _sample_sharded(sampler, noisy) * 0.5 + 0.5
@@ -517,7 +559,8 @@ def eval_condition(cfg: Dict[str, Any]) -> Dict[str, Any]:
         print("labels: ", labels)
         model = build_cfg_model(cfg)
         labels = labels.to(model.device)
-        sampler = CondGaussianDiffusionSampler(model, cfg["beta_1"], cfg["beta_T"], cfg["T"], w=cfg["w"])
+        sampler = CondGaussianDiffusionSampler(model, cfg["beta_1"], cfg["beta_T"], cfg["T"], w=cfg["w"],
+                                               **sampler_kwargs(cfg, cfg["T"]))
         img = int(cfg["img_size"])
         noisy = torch.randn(size=[cfg["batch_size"], 3, img, img], device=model.device)
         imgs = _sample_sharded(sampler, noisy, labels) * 0.5 + 0.5
@@ -561,7 +604,7 @@ def infer(cfg: Dict[str, Any]) -> Dict[str, Any]:
         torch.manual_seed(int(cfg["seed"]))
     with torch.no_grad():
         model = build_ddpm(cfg)
-        sampler = GaussianDiffusionSampler(model, cfg["beta_1"], cfg["beta_T"], cfg["T"])
+        sampler = GaussianDiffusionSampler(model, cfg["beta_1"], cfg["beta_T"], cfg["T"], **sampler_kwargs(cfg, cfg["T"]))
         img = int(cfg.get("img_size") or 256)
         x_T = torch.randn(size=[cfg["batch_size"], 3, img, img], device=model.device)
         sampled = _sample_sharded(sampler, x_T)

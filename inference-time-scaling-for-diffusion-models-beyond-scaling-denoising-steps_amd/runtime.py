@@ -42,6 +42,16 @@ class TensorView(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char_p), ("data", ctypes.c_void_p), ("numel", ctypes.c_int64)]
 
 
+class X0Schedule(ctypes.Structure):
+    """itsd_x0_schedule (include/itsd.h): host tables of K rows."""
+    _fields_ = [("K", ctypes.c_int32), ("tau", ctypes.POINTER(ctypes.c_int32))] + \
+               [(k, ctypes.POINTER(ctypes.c_float)) for k in ("a0", "b0", "c0", "cx", "sg")] + \
+               [("clip_x0", ctypes.c_int32), ("w", ctypes.c_float)]
+
+
+X0_ROW_KEYS = ("a0", "b0", "c0", "cx", "sg")
+
+
 class OpInfo(ctypes.Structure):
     """itsd_op_info (include/itsd.h)."""
     _fields_ = [(k, ctypes.c_int32) for k in (
@@ -76,6 +86,7 @@ _SIGS = {
     "itsd_unet_representation": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p],
     "itsd_set_schedule": [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                           ctypes.c_float],
+    "itsd_set_schedule_x0": [ctypes.c_void_p, ctypes.POINTER(X0Schedule)],
     "itsd_sampler_run": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                          ctypes.c_uint64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p],
     "itsd_sampler_predict_x0": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
@@ -215,6 +226,26 @@ class NativeUNet:
         check(lib().itsd_set_schedule(self.h, c1.numel(), c1.data_ptr(), c2.data_ptr(), sv.data_ptr(), float(w)))
         self.T_sched = c1.numel()
 
+    def set_schedule_x0(self, tau: Sequence[int], rows: Dict[str, torch.Tensor], clip_x0: bool, w: float = 0.0):
+        """Install an x0-form schedule (``itsd_set_schedule_x0``): ``tau`` the timestep of each row, ``rows`` the five
+        per-row tables a0, b0, c0, cx, sg (``schedule.x0_form_rows``; cast to fp32 here). ``run`` and ``predict_x0``
+        then count rows; ``set_schedule`` puts the ancestral form back."""
+        K = len(tau)
+        sc = X0Schedule()
+        sc.K = K
+        keep = [(ctypes.c_int32 * K)(*[int(t) for t in tau])]
+        sc.tau = keep[0]
+        for k in X0_ROW_KEYS:
+            v = rows[k].detach().cpu().float().contiguous()
+            if v.numel() != K:
+                raise ValueError(f"x0-form table {k} has {v.numel()} rows, tau has {K}")
+            keep.append(v)
+            setattr(sc, k, ctypes.cast(v.data_ptr(), ctypes.POINTER(ctypes.c_float)))
+        sc.clip_x0 = int(bool(clip_x0))
+        sc.w = float(w)
+        check(lib().itsd_set_schedule_x0(self.h, ctypes.byref(sc)))
+        self.T_sched = K
+
     def run(self, x: torch.Tensor, t_begin: int, t_end: int, seed: int, noise: Optional[torch.Tensor] = None,
             labels: Optional[torch.Tensor] = None, noise_offset: int = 0, graph: bool = True, clip: bool = True,
             sync: bool = True) -> None:
@@ -232,7 +263,7 @@ class NativeUNet:
         return out
 
     def query(self, key: str) -> int:
-        """itsd_unet_query: "graph_captures", "max_batch", "T_sched", "ws_bytes", "ops"."""
+        """itsd_unet_query: "graph_captures", "max_batch", "T_sched", "sched_form", "ws_bytes", "ops"."""
         v = ctypes.c_int64()
         check(lib().itsd_unet_query(self.h, key.encode(), ctypes.byref(v)))
         return int(v.value)

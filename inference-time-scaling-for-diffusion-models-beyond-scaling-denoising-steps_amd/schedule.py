@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import dataclasses
 import math
-from typing import Tuple
+from typing import Dict, List, Sequence, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -70,3 +70,45 @@ def renoise_coeffs(alphas_bar: torch.Tensor, s: int, delta: int) -> Tuple[float,
         return 1.0, 0.0
     r = float(alphas_bar[int(s) + int(delta)].double()) / float(alphas_bar[int(s)].double())
     return math.sqrt(r), math.sqrt(1.0 - r)
+
+
+def strided_timesteps(T: int, K: int) -> List[int]:
+    """The default row -> timestep map of a K-row sampler over a T-step schedule: tau[k] = ((k + 1) T) // K - 1.
+    Strictly increasing, tau[K - 1] = T - 1, and K = T is the identity."""
+    T, K = int(T), int(K)
+    if not 1 <= K <= T:
+        raise ValueError(f"steps = {K} outside [1, T={T}]")
+    return [((k + 1) * T) // K - 1 for k in range(K)]
+
+
+def check_timesteps(tau: Sequence[int], T: int) -> List[int]:
+    """An explicit row -> timestep list: strictly increasing integers in [0, T)."""
+    tau = [int(t) for t in tau]
+    if not tau:
+        raise ValueError("timesteps: empty")
+    if tau[0] < 0 or tau[-1] >= int(T) or any(b <= a for a, b in zip(tau, tau[1:])):
+        raise ValueError(f"timesteps must be strictly increasing in [0, T={int(T)})")
+    return tau
+
+
+def x0_form_rows(alphas_bar: torch.Tensor, tau: Sequence[int], eta: float) -> Dict[str, torch.Tensor]:
+    """The per-row scalars of the x0-form step (DDIM(eta) written through the x_0 estimate), fp64 [K] each:
+
+        x0 = a0 x - b0 eps  (clipped to [-1, 1] by a clip_x0 sampler);   x' = c0 x0 + cx x + sg z
+
+    With a = abar[tau[k]] and p = abar[tau[k - 1]] (p = 1 at k = 0): a0, b0 are ``x0_coeffs``' expressions,
+    sg = eta sqrt((1 - p) / (1 - a)) sqrt(1 - a / p), d = sqrt(1 - p - sg^2), c0 = sqrt(p) - d sqrt(a) / sqrt(1 - a),
+    cx = d / sqrt(1 - a). Row 0 is (c0, cx, sg) = (1, 0, 0) exactly: the last row returns the x_0 estimate."""
+    tau = [int(t) for t in tau]
+    eta = float(eta)
+    rows = {k: [] for k in ("a0", "b0", "c0", "cx", "sg")}
+    for k, t in enumerate(tau):
+        a = float(alphas_bar[t].double())
+        p = float(alphas_bar[tau[k - 1]].double()) if k else 1.0
+        a0, b0 = x0_coeffs(alphas_bar, t)
+        sg = eta * math.sqrt((1.0 - p) / (1.0 - a)) * math.sqrt(1.0 - a / p)
+        d = math.sqrt(max(1.0 - p - sg * sg, 0.0))
+        for name, v in (("a0", a0), ("b0", b0), ("c0", math.sqrt(p) - d * math.sqrt(a) / math.sqrt(1.0 - a)),
+                        ("cx", d / math.sqrt(1.0 - a)), ("sg", sg)):
+            rows[name].append(v)
+    return {k: torch.tensor(v, dtype=torch.float64) for k, v in rows.items()}

@@ -162,6 +162,8 @@ class SearchEngine:
         self.rank = dist.get_rank(group) if self.dist else 0
         if noise == "reference" and self.world > 1:
             raise ValueError("noise='reference' follows one process's global generator; use 'philox' when sharded")
+        if noise == "reference" and getattr(sampler, "sampler", "ddpm") != "ddpm":
+            raise ValueError("noise='reference' needs the ancestral sampler: the reference has no few-step draw order")
         self.noise = noise
         self.nfes = 0  # denoise calls (candidates), as search_algorithm.py:72 counts them
         self.device = sampler.model.device
@@ -332,7 +334,8 @@ class SearchEngine:
                            injection_steps: Sequence[int], keep: int, renoise_steps: int = 0, labels=None):
         """Path search that branches at intermediate steps (the reference's ``PathSearch`` docstring; its code is the
         placeholder ``path_search`` keeps). N = n_paths paths start as the placeholder's candidates. At each
-        injection step s (strictly decreasing, 1 <= s, s + renoise_steps <= T - 1) every path is denoised down to
+        injection step s (strictly decreasing, 1 <= s, s + renoise_steps <= T - 1; steps are the sampler's rows,
+        T its ``n_steps``: timesteps under the ancestral sampler) every path is denoised down to
         x_s, its x_0 estimate is scored, the ``keep`` best survive with N // keep children each, and the children are
         the survivor re-noised ``renoise_steps`` steps up (0: a copy; they then diverge through the sampler's own
         per-step noise, which is keyed by position). After the last stage the paths are denoised to the end and scored
@@ -343,7 +346,9 @@ class SearchEngine:
         part of the path -- the winning image is ``self.best_image``. hist: ``scores`` (final, N), ``stage_scores``
         [m][N], ``parents`` [m][N] (global indices), ``injection_points``, ``best_index``, ``root_index`` and
         ``unet_steps`` = N x (sampler steps run + one x_0 evaluation per stage), a guided pair counting once."""
-        T = int(self.sampler.T)
+        # rows of the sampler's schedule: timesteps for the ancestral sampler, the K rows of a few-step one (injection
+        # and re-noising steps are then rows, and abar is indexed by row)
+        T = int(getattr(self.sampler, "n_steps", self.sampler.T))
         steps = [int(s) for s in injection_steps] if isinstance(injection_steps, (list, tuple)) else None
         if not steps or any(int(s) != s for s in injection_steps):
             raise ValueError("injection_steps must be a non-empty list of ints")
@@ -366,7 +371,7 @@ class SearchEngine:
         lab = None if labels is None else labels.to(self.device).flatten().repeat(nl)
         pivot = initial_noise.to(self.device, torch.float32).contiguous()
         x = self.candidate_noise(0, g0, nl, shape, pivot, noise_scale)  # round 0: the placeholder's candidates
-        abar = self.sampler.sched.alphas_bar
+        abar = getattr(self.sampler, "abar_rows", self.sampler.sched.alphas_bar)
         t_hi, ran = T - 1, 0
         stage_scores, parents = [], []
         for i, s in enumerate(steps):

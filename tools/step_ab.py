@@ -2,6 +2,9 @@
 process, interleaved. Measurement tool, never part of the product.
 
     python tools/step_ab.py --n 32 --variants "base,sc_side=0" [--steps 50] [--rounds 3]
+
+--samplers ddpm,ddim times the ancestral step and the x0-form step (every timestep a row, so both run the same UNet
+evaluations; --eta, --clip-x0) side by side, interleaved like the variants.
 """
 import argparse
 import os
@@ -35,6 +38,9 @@ def main():
     ap.add_argument("--create-set", default="", help="options set before the UNet is created, e.g. attn_fuse=0")
     ap.add_argument("--lib", default="", help="another build of libitsd_hip.so (A/B of two builds in two processes)")
     ap.add_argument("--arch", default="a", help="a: Arch A; c: the C3 leg (Arch C CondUNet, CFG w=1.8: --n is N, 2N guided)")
+    ap.add_argument("--samplers", default="ddpm", help="ddpm (the ancestral step), ddim (the x0-form step), or both: ddpm,ddim")
+    ap.add_argument("--eta", type=float, default=1.0, help="ddim: eta (0: no draw at all)")
+    ap.add_argument("--clip-x0", type=int, default=1, help="ddim: clip the x_0 estimate (0 | 1)")
     args = ap.parse_args()
     if args.lib:
         rt.LIB_PATH = os.path.abspath(args.lib)
@@ -49,20 +55,25 @@ def main():
         c = ARCH_C
         net = CondUNet(c.T, c.num_labels, c.ch, c.ch_mult, c.num_res_blocks, 0.0, img_size=args.img, precision="bf16",
                        weights="gauss").to("cuda:0")
-        smp = CondGaussianDiffusionSampler(net, 1e-4, 0.028, 1000, w=1.8)
+        make = lambda **kw: CondGaussianDiffusionSampler(net, 1e-4, 0.028, 1000, w=1.8, **kw)
         run_kw["labels"] = (torch.arange(args.n, device="cuda") % 10 + 1).to(torch.int32)
     else:
         a = ARCH_A
         net = UNet(a.T, a.ch, a.ch_mult, a.attn, a.num_res_blocks, 0.0, img_size=args.img, precision="bf16",
                    weights="gauss").to("cuda:0")
-        smp = GaussianDiffusionSampler(net, 1e-4, 0.02, 1000)
+        make = lambda **kw: GaussianDiffusionSampler(net, 1e-4, 0.02, 1000, **kw)
+    kinds = args.samplers.split(",")
+    smps = {k: make() if k == "ddpm" else make(sampler="ddim", steps=1000, eta=args.eta, clip_x0=bool(args.clip_x0))
+            for k in kinds}
     x = torch.randn(args.n, 3, args.img, args.img, device="cuda")
-    variants = args.variants.split(",")
+    variants = [v if len(kinds) == 1 else f"{v}/{k}" for v in args.variants.split(",") for k in kinds]
     res = {v: [] for v in variants}
     for r in range(args.rounds):
         for v in variants:
+            smp = smps[v.rsplit("/", 1)[1] if len(kinds) > 1 else kinds[0]]
+            v_opts = v.rsplit("/", 1)[0] if len(kinds) > 1 else v
             opts = {}
-            for kv in v.split("+"):
+            for kv in v_opts.split("+"):
                 if "=" in kv:
                     k, val = kv.split("=")
                     opts[k] = int(val)
