@@ -29,6 +29,11 @@
  *                                   223-248, 262-287), batched per candidate
  *   itsd_verify_paired           <- SelfSupervisedVerifier.score(images, reference_features)
  *                                   (search/verifier.py:235-240)
+ *   itsd_verify_denoise          <- (no reference counterpart) the diffusion model as its own verifier: the squared
+ *                                   denoising error of a candidate image, under its label and under the null label.
+ *                                   Every verifier of the reference that sees content (SupervisedVerifier, CLIPScore,
+ *                                   IntegratedVerifier, search/verifier.py:69-188, 290-388) needs downloaded CLIP /
+ *                                   DINO weights; this one needs only the checkpoint already on the device
  *   itsd_attention               <- AttnBlock core softmax(q k^T C^-0.5) v
  *                                   (Diffusion/Model.py:152-161, ModelCondition.py:105-115)
  *   itsd_profile_forward / _ops / _op, itsd_unet_query, itsd_set_option
@@ -200,6 +205,28 @@ int itsd_verify(int kind, const float* images, int n_cand, int b, int c, int h, 
 int itsd_verify_paired(const float* images, const float* ref_features, int n_cand, int c, int h, int w,
                        double* scores, void* stream);
 
+/* One denoising-error probe of n images at row t of the installed schedule:
+ *   x_t = (a x0) + (b z);  sse[i][0] = sum_e (z - eps_c(x_t, t, label_i))^2;
+ *   sse[i][1] = sum_e (z - eps_u(x_t, t))^2  (CFG, eps_u under label 0; DDPM: 0).  x0 [n,3,H,W] is only read.
+ * z is ONE field [3][H][W] shared by every image of the call: noise (device fp32) when non-NULL, else Philox keyed
+ * (seed, stream_id, element within the image) -- itsd_noise's draw for one candidate. A sum is therefore a function of
+ * (image, label, seed / field, t) alone: not of n, of the image's place in the batch, or of its neighbours. t means
+ * what it means for itsd_sampler_predict_x0 (a timestep, or a row of an x0-form schedule: the time embedding is
+ * tau[t]'s); the caller passes a = sqrt(abar), b = sqrt(1 - abar) of that row (fp64 on the host, cast). The forward is
+ * the sampler step's own program (the doubled cond||uncond batch for CFG) and is NOT guided: the two errors come from
+ * the two branches. All arithmetic on z is fp32 without contraction; every block of the tail sums its elements in a
+ * fixed order and a second launch adds each image's block sums in block order in fp64 (no atomics: bit-reproducible).
+ * sse: device fp64 [n][2]. xt_out (NULL ok) receives x_t [n,3,H,W]; eps_out (NULL ok) the unguided eps,
+ * [1 (DDPM) or 2 (CFG: cond, then uncond)][n][3][H][W]: both for tests, NULL in production. Runs eagerly on the
+ * handle's stream: no step graph is captured or evicted, the NaN flag and the run parameters of the last
+ * itsd_sampler_run are left alone, and the hand-off status word ("status") is this forward's. The probe's x_t and
+ * the tail's per-block sums live in two library-owned buffers allocated at the first call (itsd_unet_poison fills
+ * them too). ITSD_ERR_INVALID with a message before any HIP call: null u / x0 / sse, no schedule installed, CFG
+ * without labels, n outside [1, max_batch], t outside [0, T_sched). */
+int itsd_verify_denoise(itsd_unet* u, const float* x0, const int32_t* labels, int n, int t, float a, float b,
+                        uint64_t seed, uint32_t stream_id, const float* noise, double* sse, float* xt_out,
+                        float* eps_out, void* stream);
+
 /* AttnBlock core on n images of S tokens, width C (single head):
  *   out[i][s][:] = softmax_j(q_s . k_j * C^-0.5) v_j
  * qkv: [n][S][3C] (q | k | v per token, the fused projection the UNet produces);
@@ -322,7 +349,8 @@ enum { ITSD_READ_ACT = 0, ITSD_READ_STATS = 1, ITSD_READ_COEF = 2, ITSD_READ_PRO
 int itsd_unet_read(itsd_unet* u, int what, int id, int n, void* dst, int64_t bytes, void* stream);
 /* Fill every buffer a forward overwrites completely with NaN bits (bf16 0xFFFF, fp32 0xFFFFFFFF), stream-ordered:
  * the activation arena (activations, channel-major V, coef buffers and the statistics slabs -- every producer
- * stores its slots plainly, none accumulates) and the split-K workspace. Left alone: what the program increments or
+ * stores its slots plainly, none accumulates), the split-K workspace and, once allocated, itsd_verify_denoise's two
+ * scratch buffers. Left alone: what the program increments or
  * needs zero between launches (split-K tickets, the AttnBlock hand-off counters, the NaN / status words, the zero
  * page), the weights, proj_buf and the embedding tables. A forward afterwards must give the bits it gives on a fresh
  * handle: a NaN or a changed value means a launch read something no launch of that forward wrote. */

@@ -58,6 +58,8 @@ hipError_t launch_noise(float*, const float*, int, long long, float, unsigned lo
                         hipStream_t);
 hipError_t launch_branch(float*, const float*, const int*, int, long long, float, float, unsigned long long, unsigned,
                          long long, hipStream_t);
+hipError_t launch_probe_noise(float*, const float*, const float*, int, long long, float, float, unsigned long long,
+                              unsigned, hipStream_t);
 template <typename T> hipError_t launch_nhwc_to_nchw(const void*, float*, int, int, int, hipStream_t);
 }  // namespace itsd
 
@@ -217,6 +219,10 @@ struct itsd_unet {
   RunParams* d_run = nullptr;
   float* x_state = nullptr;     // [max_batch][3][H][W]: the sampler's x between the caller's copies
   int32_t* lab_state = nullptr; // [max_batch] labels of the guided sampler
+  // itsd_verify_denoise's scratch, allocated at its first call: the noised probe x_t [max_batch][3][H][W] and the tail's
+  // per-block partial pairs [max_batch][H W / 64 blocks at most][2]
+  float* vd_xt = nullptr;
+  float* vd_part = nullptr;
   long long graph_captures = 0;  // step graphs captured + instantiated (itsd_unet_query)
   void* zero_page = nullptr;  // 256 KiB of zeros (conv DMA source for padding, conv.hip zero_of_block)
   float* splitk_ws = nullptr;  // split-K partial tiles (shared by all convs: they run in stream order)
@@ -1337,6 +1343,10 @@ int check_batch(itsd_unet* u, int n) {
   return ITSD_OK;
 }
 
+// itsd_verify_denoise's two scratch buffers (itsd_unet::vd_xt, vd_part): the smallest tail block is 64 pixels
+size_t vd_xt_bytes(const itsd_unet* u) { return (size_t)u->d.max_batch * 3 * u->H * u->H * 4; }
+size_t vd_part_bytes(const itsd_unet* u) { return (size_t)u->d.max_batch * ((u->H * u->H + 63) / 64) * 2 * 4; }
+
 // The two pass shapes. forward: one time-embedding row an image (proj_buf, from temb_rows), the batch as given, the
 // tail writes eps to eps_out.
 RunCtx forward_ctx(const itsd_unet* u, int n, const float* x, const int32_t* labels, float* eps_out) {
@@ -1670,6 +1680,8 @@ int itsd_unet_destroy(itsd_unet* u) {
   hipFree(u->splitk_ws);
   hipFree(u->tickets);
   hipFree(u->attn_sync);
+  hipFree(u->vd_xt);
+  hipFree(u->vd_part);
   if (u->stream) hipStreamDestroy(u->stream);
   if (u->ev_in) hipEventDestroy(u->ev_in);
   if (u->ev_out) hipEventDestroy(u->ev_out);
@@ -1841,6 +1853,40 @@ int itsd_sampler_predict_x0(itsd_unet* u, const float* x, const int32_t* labels,
   u->last_forward_n = 0;  // (the tail input is overwritten: itsd_unet_representation refuses until the next forward)
   RunCtx c = step_ctx(u, n, const_cast<float*>(x), labels);
   c.tail.step_mode = 2; c.tail.a0 = a0; c.tail.b0 = b0; c.tail.x0_out = x0;
+  HIPCHK(launch_set_int(u->d_t, t, s));
+  HIPCHK(hipMemsetAsync(u->d_nan + 1, 0, 4, s));  // this forward's hand-off status (itsd_unet_query "status")
+  CHK(run_program(u, c, resolve_program(u, c), s));
+  return leave_stream(u, cs);
+}
+
+// One denoising-error probe: x0 noised to row t with the probe's own noise field (probe_noise_kernel, into the handle's
+// scratch), then the sampler step's program on it -- as itsd_sampler_predict_x0: the doubled cond||uncond batch for
+// CFG, the time-embedding row selected on the device -- with the tail's sse epilogue (TailArgs::step_mode 4), which
+// re-draws the same field and leaves sse[n][2]. Eager: no step graph is captured, looked up or evicted, and the
+// sampler's run parameters and NaN flag stay as the last run left them.
+int itsd_verify_denoise(itsd_unet* u, const float* x0, const int32_t* labels, int n, int t, float a, float b,
+                        uint64_t seed, uint32_t stream_id, const float* noise, double* sse, float* xt_out,
+                        float* eps_out, void* stream) {
+  if (!u || !x0 || !sse) return fail(ITSD_ERR_INVALID, "itsd_verify_denoise: null argument");
+  if (!u->T_sched) return fail(ITSD_ERR_INVALID, "itsd_verify_denoise: no schedule installed (itsd_set_schedule / _x0)");
+  if (u->cfg && !labels) return fail(ITSD_ERR_INVALID, "itsd_verify_denoise: a CFG UNet needs labels");
+  CHK(check_batch(u, n));
+  if (t < 0 || t >= u->T_sched)
+    return fail(ITSD_ERR_INVALID, "itsd_verify_denoise: step " + std::to_string(t) + " outside [0, T_sched=" +
+                                      std::to_string(u->T_sched) + ")");
+  hipStream_t cs = (hipStream_t)stream;
+  hipStream_t s = u->stream;
+  CHK(enter_stream(u, cs));
+  if (!u->vd_xt) HIPCHK(hipMalloc(&u->vd_xt, vd_xt_bytes(u)));
+  if (!u->vd_part) HIPCHK(hipMalloc(&u->vd_part, vd_part_bytes(u)));
+  u->last_forward_n = 0;  // (the tail input is overwritten: itsd_unet_representation refuses until the next forward)
+  const long long per = 3ll * u->H * u->H;
+  HIPCHK(launch_probe_noise(u->vd_xt, x0, noise, n, per, a, b, seed, stream_id, s));
+  if (xt_out) HIPCHK(hipMemcpyAsync(xt_out, u->vd_xt, (size_t)n * per * 4, hipMemcpyDeviceToDevice, s));
+  RunCtx c = step_ctx(u, n, u->vd_xt, labels);
+  TailArgs& ta = c.tail;
+  ta.step_mode = 4; ta.noise = noise; ta.vseed = seed; ta.vstream = stream_id;
+  ta.vpart = u->vd_part; ta.vsse = sse; ta.eps_out = eps_out;
   HIPCHK(launch_set_int(u->d_t, t, s));
   HIPCHK(hipMemsetAsync(u->d_nan + 1, 0, 4, s));  // this forward's hand-off status (itsd_unet_query "status")
   CHK(run_program(u, c, resolve_program(u, c), s));
@@ -2153,6 +2199,9 @@ int itsd_unet_poison(itsd_unet* u, void* stream) {
   // build): all of them stored whole by their producers
   HIPCHK(hipMemsetAsync(u->ws, 0xFF, u->ws_bytes, u->stream));
   HIPCHK(hipMemsetAsync(u->splitk_ws, 0xFF, (size_t)itsd_unet::kSplitkCap * 4, u->stream));
+  // itsd_verify_denoise's scratch (once it exists): the call stores every element it reads
+  if (u->vd_xt) HIPCHK(hipMemsetAsync(u->vd_xt, 0xFF, vd_xt_bytes(u), u->stream));
+  if (u->vd_part) HIPCHK(hipMemsetAsync(u->vd_part, 0xFF, vd_part_bytes(u), u->stream));
   u->last_forward_n = 0;  // (the tail input is gone: itsd_unet_representation refuses until the next forward)
   return leave_stream(u, cs);
 }

@@ -318,7 +318,8 @@ struct TailArgs {
   float guide_w1;       // (1 + w) computed in double then cast, as the reference's scalar
   // mode
   int step_mode;        // 0: write eps NCHW; 1: sampler update of x in place; 2: x0_out = clip(a0 x - b0 eps) (x read only);
-                        // 3: the x0-form update of x in place (rows of xrow, below)
+                        // 3: the x0-form update of x in place (rows of xrow, below); 4: the denoising-error sums (last
+                        // fields, below)
   float* eps_out;       // NCHW [n][3][H][W]
   float* x;             // NCHW [n][3][H][W]
   const int* tsel;      // current step t (device)
@@ -340,6 +341,16 @@ struct TailArgs {
   // row), run and nan_flag as in step_mode 1; coeff1 / coeff2 / sqrt_var are not read
   const float* xrow[5];
   int clip_x0;
+  // step_mode 4 (itsd_verify_denoise): the denoising-error probe. Nothing is guided and nothing of the step's is read:
+  // z[e] = noise[e] (here ONE field [3][H][W], shared by every image) or Philox (vseed, vstream, e), e the element
+  // within the image; each block stores its (sum (z - eps_c)^2, sum (z - eps_u)^2) as one fp32 pair at
+  // vpart[blockIdx.x] (blocks are image-major and never straddle two images) and tail_sse_finalize_kernel sums each
+  // image's pairs in block order in fp64 into vsse[n][2]. eps_out, when non-null, receives the unguided
+  // eps [1 or 2][n][3][H][W] (cond, then uncond). x is not read.
+  unsigned long long vseed;
+  unsigned vstream;
+  float* vpart;
+  double* vsse;
 };
 
 constexpr int kBranchChunk = 256;  // parent-table rows a branch_kernel launch carries in its arguments (1 KiB)

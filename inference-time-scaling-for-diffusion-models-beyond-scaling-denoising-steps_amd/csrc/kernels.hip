@@ -1456,7 +1456,8 @@ __device__ __forceinline__ float philox_normal(unsigned long long seed, unsigned
 // ============================================================================ tail conv + sampler step
 // tail = GN -> Swish -> Conv2d(C, 3, 3, padding=1) (Model.py:252-256, 282). The GN+Swish
 // output g is produced by groupnorm_kernel (tail_mfma_kernel applies it itself); the three kernels below do the
-// 3-output conv per pixel and hand each output element's eps to tail_finish, which ends in one of four ways:
+// 3-output conv per pixel and hand each output element's eps to tail_finish (tail_sse_item for the last), which ends in
+// one of five ways:
 //   eps  (TailArgs::step_mode 0, the forward API)  eps_out = eps
 //   step (step_mode 1)  the ancestral update of Diffusion.py:67-71,96-100 in place on x:
 //          mean = coeff1[t]*x - coeff2[t]*eps ;  x = mean + sqrt(var[t]) * z  (z = 0 at t = 0; injected or Philox),
@@ -1471,9 +1472,19 @@ __device__ __forceinline__ float philox_normal(unsigned long long seed, unsigned
 //          (no contraction: the tests demand these bits). z is noise[k] or Philox (seed, k, noise_offset + o); where
 //          sg == 0 it is neither drawn nor read (wave-uniform: one row a launch). NaN test, clip_at clip and the
 //          flag as in the ancestral step.
+//   sse  (step_mode 4, its own instantiation too)  the denoising-error probe of itsd_verify_denoise: with z[e] the
+//          probe's noise at element e = o mod 3HW of the image (noise[e], or Philox (vseed, vstream, e): one field
+//          shared by every image), q_c = (z - eps_c)^2 and, CFG, q_u = (z - eps_u)^2 in fp32 without contraction --
+//          NOT guided: the two branches stay apart. x is neither read nor written; the NaN flag, the step counter,
+//          a.run and the schedule tables are not touched. Each block sums its items' q in an order fixed by the
+//          item's place in the block (the thread's own items in order, a lane butterfly, then the wave partials in
+//          wave order by thread 0: tail_sse_block) and stores one fp32 pair to vpart[blockIdx.x] with a plain store;
+//          tail_sse_finalize_kernel adds each image's pairs in block order in fp64. No atomics: a sum is a function
+//          of (image, label, z) alone, whatever the batch or the image's place in it. eps_out (debug, NULL in
+//          production) receives the unguided eps [1 or 2][n][3][H][W].
 // CFG: eps = (1+w) eps_c - w eps_u (DiffusionCondition.py:85) with the unconditional
-// branch at image index img + n of g (guided before tail_finish, in all four modes).
-// EPI, the kernels' template parameter, names the instantiation: 0 eps / step, 1 x0, 2 x0 step.
+// branch at image index img + n of g (guided before tail_finish, in the first four modes).
+// EPI, the kernels' template parameter, names the instantiation: 0 eps / step, 1 x0, 2 x0 step, 3 sse.
 __device__ __forceinline__ float tail_x0(float a0, float b0, float xv, float e) {
 #pragma clang fp contract(off)
   const float v = a0 * xv - b0 * e;
@@ -1566,6 +1577,51 @@ __device__ __forceinline__ bool tail_finish(const TailArgs& a, const TailStep& s
   return bad;
 }
 
+// The sse epilogue's output element: its unguided pair (ec, eu; eu is read for CFG only), its NCHW offset o in image
+// img. Adds its squared errors to the thread's sums qc / qu.
+__device__ __forceinline__ void tail_sse_item(const TailArgs& a, size_t o, int img, float ec, float eu, float& qc,
+                                              float& qu) {
+#pragma clang fp contract(off)
+  const size_t per = (size_t)3 * (a.H * a.W), e = o - (size_t)img * per;
+  const float z = a.noise ? a.noise[e] : philox_normal(a.vseed, a.vstream, (unsigned long long)e);
+  const float dc = z - ec;
+  const float sc = dc * dc;
+  qc = qc + sc;
+  if (a.cfg) {
+    const float du = z - eu;
+    const float su = du * du;
+    qu = qu + su;
+  }
+  if (a.eps_out) {
+    a.eps_out[o] = ec;
+    if (a.cfg) a.eps_out[(size_t)a.n * per + o] = eu;
+  }
+}
+
+// The sse epilogue's block reduction, reached by every thread of the block (NW waves): lane butterfly, the wave
+// partials through LDS (scratch: >= 2 NW floats of the block's shared memory that nothing reads any more once every
+// thread is here), summed in wave order by thread 0, one plain store of the pair.
+template <int NW>
+__device__ __forceinline__ void tail_sse_block(const TailArgs& a, float* scratch, float qc, float qu) {
+  qc = wave_sum(qc);
+  qu = wave_sum(qu);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) {
+    scratch[(threadIdx.x >> 6) * 2] = qc;
+    scratch[(threadIdx.x >> 6) * 2 + 1] = qu;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float sc = scratch[0], su = scratch[1];
+    for (int w = 1; w < NW; ++w) {
+      sc += scratch[2 * w];
+      su += scratch[2 * w + 1];
+    }
+    a.vpart[(size_t)blockIdx.x * 2] = sc;
+    a.vpart[(size_t)blockIdx.x * 2 + 1] = su;
+  }
+}
+
 // reference layout w[co][ci][ky][kx] -> wl[(tap*C + ci)*3 + co] (256 threads)
 __device__ __forceinline__ void tail_stage_weights(float* wl, const float* w, int C) {
   for (int i = threadIdx.x; i < 27 * C; i += 256) {
@@ -1617,6 +1673,14 @@ __global__ __launch_bounds__(256) void tail_kernel(TailArgs a) {
   };
   float eps[3];
   conv3(img, eps[0], eps[1], eps[2]);
+  if constexpr (EPI == 3) {  // (the launcher admits H W % 256 == 0 only: no thread returned above)
+    float u[3] = {0.f, 0.f, 0.f}, qc = 0.f, qu = 0.f;
+    if (a.cfg) conv3(img + a.n, u[0], u[1], u[2]);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) tail_sse_item(a, ((size_t)img * 3 + c) * HW + rem, img, eps[c], u[c], qc, qu);
+    tail_sse_block<4>(a, wl, qc, qu);
+    return;
+  }
   if (a.cfg) {
 #pragma clang fp contract(off)
     float u[3];
@@ -1697,6 +1761,19 @@ __global__ __launch_bounds__(256) void tail2_kernel(TailArgs a) {
     rp[0] = s0; rp[1] = s1; rp[2] = s2;
   }
   __syncthreads();
+  if constexpr (EPI == 3) {  // as below, the two branches kept apart; threads 192.. hold no item
+    float qc = 0.f, qu = 0.f;
+    if (tid < 192) {
+      const int opx = tid / 3, oc = tid - opx * 3;
+      float s = 0.f, su = 0.f;
+      for (int w = 0; w < 4; ++w) s += red[(w * 64 + opx) * 3 + oc];
+      if (a.cfg)
+        for (int w = 0; w < 4; ++w) su += red[((4 + w) * 64 + opx) * 3 + oc];
+      tail_sse_item(a, tail_offset(img, y0, opx, oc, H, W), img, a.b[oc] + s, a.b[oc] + su, qc, qu);
+    }
+    tail_sse_block<4>(a, wl, qc, qu);
+    return;
+  }
   if (tid >= 192) return;
   const int opx = tid / 3, oc = tid - opx * 3;  // (pixel, output channel), channel quarters summed in order
   float e = a.b[oc];
@@ -1763,7 +1840,7 @@ __global__ __launch_bounds__(NTH, 2) void tail_mfma_kernel(TailArgs a) {
   constexpr int TIT = (TM_PX * 3 + NTH - 1) / NTH;
   float xpre[TIT] = {};
   TailStep st;
-  if (EPI || a.step_mode) {
+  if ((EPI || a.step_mode) && EPI != 3) {
     st = tail_step_load<EPI>(a);
 #pragma unroll
     for (int k = 0; k < TIT; ++k) {
@@ -1854,6 +1931,20 @@ __global__ __launch_bounds__(NTH, 2) void tail_mfma_kernel(TailArgs a) {
     }
   }
   __syncthreads();
+  if constexpr (EPI == 3) {  // the red[] rows of both passes, unguided
+    float qc = 0.f, qu = 0.f;
+#pragma unroll
+    for (int k = 0; k < TIT; ++k) {
+      const int it = tid + NTH * k;
+      if (it >= TM_PX * 3) break;
+      const int opx = it / 3, oc = it - opx * 3;
+      const float ec = red[opx * 3 + oc] + a.b[oc];
+      const float eu = a.cfg ? red[(TM_PX + opx) * 3 + oc] + a.b[oc] : 0.f;
+      tail_sse_item(a, tail_offset(img, y0, opx, oc, H, W), img, ec, eu, qc, qu);
+    }
+    tail_sse_block<NW>(a, (float*)tsm, qc, qu);
+    return;
+  }
 #pragma unroll
   for (int k = 0; k < TIT; ++k) {
     const int it = tid + NTH * k;
@@ -1882,8 +1973,20 @@ static bool tail_mfma_ok_px(int px, int H, int W, int C) {
 size_t tail_mfma_smem(int H, int W, int C) { return tail_mfma_smem_px(128, H, W, C); }
 bool tail_mfma_ok(int H, int W, int C) { return tail_mfma_ok_px(128, H, W, C); }
 
-// step_mode 2 needs its operands (and nothing of the step's); step_mode 3 its tables and the step's run state
+// step_mode 4's second launch: sse[img][k] = sum over the image's bpi block pairs, in block order, in fp64
+__global__ __launch_bounds__(64) void tail_sse_finalize_kernel(const float* part, int bpi, int n2, double* sse) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n2) return;
+  const float* p = part + (size_t)(i >> 1) * bpi * 2 + (i & 1);
+  double s = 0.0;
+  for (int b = 0; b < bpi; ++b) s += (double)p[2 * b];
+  sse[i] = s;
+}
+
+// step_mode 2 needs its operands (and nothing of the step's); step_mode 3 its tables and the step's run state;
+// step_mode 4 its two outputs
 static bool tail_x0_ok(const TailArgs& a) {
+  if (a.step_mode == 4) return a.vpart && a.vsse;
   if (a.step_mode == 3) {
     for (const float* p : a.xrow)
       if (!p) return false;
@@ -1893,18 +1996,26 @@ static bool tail_x0_ok(const TailArgs& a) {
 }
 
 // The body of a tail launcher from its launch geometry on: launches the instantiation a.step_mode selects (X0K for the
-// x0 epilogue, XSK for the x0-form step, PLAIN for eps and step; each under its own name, which the census and the
-// profiles key on) and returns the launch's status. BIG: the three may use up to kTailSmemMax of dynamic shared
-// memory; the attribute is set once.
-#define ITSD_RETURN_TAIL_LAUNCH(PLAIN, X0K, XSK, BIG, grid, block, sm, s, a)                                   \
+// x0 epilogue, XSK for the x0-form step, SSEK for the denoising-error sums, PLAIN for eps and step; each under its own
+// name, which the census and the profiles key on) and returns the launch's status. BIG: the four may use up to
+// kTailSmemMax of dynamic shared memory; the attribute is set once. SSEK is followed by its finalize launch, and is
+// refused where a block would straddle two images (the grid is not a whole number of blocks an image).
+#define ITSD_RETURN_TAIL_LAUNCH(PLAIN, X0K, XSK, SSEK, BIG, grid, block, sm, s, a)                             \
   do {                                                                                                         \
     static bool attr = !(BIG);                                                                                 \
     if (!attr) {                                                                                               \
-      for (const void* f : {(const void*)PLAIN, (const void*)X0K, (const void*)XSK}) {                         \
+      for (const void* f : {(const void*)PLAIN, (const void*)X0K, (const void*)XSK, (const void*)SSEK}) {      \
         hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTailSmemMax);  \
         if (e != hipSuccess) return e;                                                                         \
       }                                                                                                        \
       attr = true;                                                                                             \
+    }                                                                                                          \
+    if ((a).step_mode == 4) {                                                                                  \
+      if ((a).n < 1 || (grid).x % (a).n) return hipErrorInvalidValue;                                          \
+      ITSD_LAUNCH(SSEK, grid, block, sm, s, a);                                                                \
+      ITSD_LAUNCH(tail_sse_finalize_kernel, dim3((2 * (a).n + 63) / 64), dim3(64), 0, s, (a).vpart,            \
+                  (int)((grid).x / (a).n), 2 * (a).n, (a).vsse);                                               \
+      return hipGetLastError();                                                                                \
     }                                                                                                          \
     if ((a).step_mode == 2) ITSD_LAUNCH(X0K, grid, block, sm, s, a);                                           \
     else if ((a).step_mode == 3) ITSD_LAUNCH(XSK, grid, block, sm, s, a);                                      \
@@ -1917,7 +2028,7 @@ hipError_t launch_tail_mfma(const TailArgs& a, hipStream_t s) {
   const dim3 grid(a.n * (a.H / (128 / a.W)));
   const size_t sm = tail_mfma_smem_px(128, a.H, a.W, a.C);
   ITSD_RETURN_TAIL_LAUNCH((tail_mfma_kernel<128, 512>), (tail_mfma_kernel<128, 512, 1>), (tail_mfma_kernel<128, 512, 2>),
-                          true, grid, dim3(512), sm, s, a);
+                          (tail_mfma_kernel<128, 512, 3>), true, grid, dim3(512), sm, s, a);
 }
 
 template <typename T>
@@ -1927,13 +2038,14 @@ hipError_t launch_tail(const TailArgs& a, hipStream_t s) {
     const size_t sm = 27 * a.C * 4 + (size_t)(64 / a.W + 2) * (a.W + 2) * (a.C * sizeof(T) + 16) + 2 * 4 * 64 * 3 * 4;
     if (sm > kTailSmemMax) return hipErrorInvalidValue;
     const dim3 grid(a.n * (a.H / (64 / a.W)));
-    ITSD_RETURN_TAIL_LAUNCH(tail2_kernel<T>, (tail2_kernel<T, 1>), (tail2_kernel<T, 2>), true, grid, dim3(256), sm, s,
-                            a);
+    ITSD_RETURN_TAIL_LAUNCH(tail2_kernel<T>, (tail2_kernel<T, 1>), (tail2_kernel<T, 2>), (tail2_kernel<T, 3>), true, grid,
+                            dim3(256), sm, s, a);
   }
   const long long total = (long long)a.n * a.H * a.W;
   const dim3 grid((unsigned)((total + 255) / 256));
-  ITSD_RETURN_TAIL_LAUNCH(tail_kernel<T>, (tail_kernel<T, 1>), (tail_kernel<T, 2>), false, grid, dim3(256),
-                          27 * a.C * sizeof(float), s, a);
+  if (a.step_mode == 4 && (a.H * a.W) % 256) return hipErrorInvalidValue;  // (a block of 256 pixels would straddle)
+  ITSD_RETURN_TAIL_LAUNCH(tail_kernel<T>, (tail_kernel<T, 1>), (tail_kernel<T, 2>), (tail_kernel<T, 3>), false, grid,
+                          dim3(256), 27 * a.C * sizeof(float), s, a);
 }
 template hipError_t launch_tail<float>(const TailArgs&, hipStream_t);
 template hipError_t launch_tail<bf16_t>(const TailArgs&, hipStream_t);
@@ -2175,6 +2287,56 @@ hipError_t launch_branch(float* dst, const float* src, const int* parents, int n
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
+}
+
+// The probe noising of itsd_verify_denoise: xt[i][e] = (a x0[i][e]) + (b z[e]) for i < n, e < per, fp32 without
+// contraction, z[e] = noise[e] or Philox (seed, stream_id, e): ONE field, indexed by the element within the image and
+// shared by every image (the draw tail_sse_item repeats). grid = (element blocks, groups of kProbeImgs images: the
+// draw is made once a group); VEC: 16-B accesses, 4 elements a thread (per % 4 == 0, all bases 16-B aligned).
+constexpr int kProbeImgs = 8;
+template <bool VEC>
+__global__ __launch_bounds__(256) void probe_noise_kernel(float* xt, const float* x0, const float* noise, int n,
+                                                          long long per, float a, float b, unsigned long long seed,
+                                                          unsigned stream_id) {
+#pragma clang fp contract(off)
+  constexpr int V = VEC ? 4 : 1;
+  const long long e0 = ((long long)blockIdx.x * 256 + threadIdx.x) * V;
+  if (e0 >= per) return;
+  float bz[V];
+  if constexpr (VEC) {
+    f32x4 z4;
+    if (noise) z4 = *(const f32x4*)(noise + e0);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) bz[k] = b * (noise ? z4[k] : philox_normal(seed, stream_id, (unsigned long long)(e0 + k)));
+  } else {
+    bz[0] = b * (noise ? noise[e0] : philox_normal(seed, stream_id, (unsigned long long)e0));
+  }
+  const int i0 = blockIdx.y * kProbeImgs, i1 = i0 + kProbeImgs < n ? i0 + kProbeImgs : n;
+  for (int i = i0; i < i1; ++i) {
+    const long long o = (long long)i * per + e0;
+    if constexpr (VEC) {
+      const f32x4 p = *(const f32x4*)(x0 + o);
+      f32x4 r;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float ax = a * p[k];
+        r[k] = ax + bz[k];
+      }
+      *(f32x4*)(xt + o) = r;
+    } else {
+      const float ax = a * x0[o];
+      xt[o] = ax + bz[0];
+    }
+  }
+}
+hipError_t launch_probe_noise(float* xt, const float* x0, const float* noise, int n, long long per, float a, float b,
+                              unsigned long long seed, unsigned stream_id, hipStream_t s) {
+  const bool vec = per % 4 == 0 && ((uintptr_t)xt | (uintptr_t)x0 | (uintptr_t)noise) % 16 == 0;
+  const long long items = vec ? per / 4 : per;
+  const dim3 grid((unsigned)((items + 255) / 256), (unsigned)((n + kProbeImgs - 1) / kProbeImgs));
+  if (vec) ITSD_LAUNCH(probe_noise_kernel<true>, grid, dim3(256), 0, s, xt, x0, noise, n, per, a, b, seed, stream_id);
+  else ITSD_LAUNCH(probe_noise_kernel<false>, grid, dim3(256), 0, s, xt, x0, noise, n, per, a, b, seed, stream_id);
+  return hipGetLastError();
 }
 
 // ============================================================================ representation

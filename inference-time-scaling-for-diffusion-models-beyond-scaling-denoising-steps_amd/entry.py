@@ -30,8 +30,17 @@ Keys beyond the reference (all optional):
         n_paths: 4               # path
         injection_step: 400
         noise_scale: 0.1
-        verifier: oracle         # oracle | selfsup | aesthetic
+        verifier: oracle         # oracle | selfsup | aesthetic | denoise | class
+        verifier_probes: 4       # denoise / class: UNet evaluations an image (rows spread over the sampler's
+                                 # schedule), or an explicit list of rows
+        verifier_seed: 0         # denoise / class: Philox key of the probes' noise fields
         bestImgName: SearchBestImgs.png
+
+  ``denoise`` and ``class`` score with the diffusion model itself (``itsd.verifier.DenoisingVerifier``, no reference
+  counterpart: the reference's content-aware verifiers need downloaded CLIP / DINO weights): the squared error of the
+  model's eps prediction on the candidate image re-noised to a few rows. ``denoise`` is minus that error (under the
+  image's label for a conditional model); ``class`` is the error under the null label minus the error under the label,
+  and needs the conditional eval: without labels it raises a ValueError naming ``search.verifier``.
 
 * ``sampler``: a block selecting the sampler of the eval AND of the ``search`` block's rounds (no reference
   counterpart: the reference has the ancestral sampler only). Absent, or ``kind: ddpm``: the ancestral sampler::
@@ -426,16 +435,46 @@ def sampler_kwargs(cfg: Dict[str, Any], T: int) -> Dict[str, Any]:
     return {"sampler": "ddim", "steps": steps, "eta": float(eta), "clip_x0": clip}
 
 
+def search_verifier(s: Dict[str, Any], sampler, has_labels: bool):
+    """The ``search`` block's verifier object. ``denoise`` / ``class`` build a ``DenoisingVerifier`` over the round's
+    own sampler from ``verifier_probes`` (an int, or a list of rows) and ``verifier_seed``; every bad value raises a
+    ValueError that names its key."""
+    from .verifier import VERIFIERS, DenoisingVerifier
+
+    vname = (s.get("verifier") or "oracle")
+    vname = vname.lower() if isinstance(vname, str) else vname
+    if vname not in VERIFIERS:
+        raise ValueError(f"unknown search.verifier '{vname}' ({' | '.join(VERIFIERS)})")
+    model_keys = [k for k in ("verifier_probes", "verifier_seed") if s.get(k) is not None]
+    if VERIFIERS[vname] is not DenoisingVerifier:
+        if model_keys:
+            raise ValueError(f"search.{model_keys[0]} belongs to search.verifier: denoise | class")
+        return VERIFIERS[vname]()
+    if vname == "class" and not has_labels:
+        raise ValueError("search.verifier class scores an image against its label: it needs the conditional eval "
+                         "(labels); use search.verifier: denoise for an unconditional model")
+    probes, seed = s.get("verifier_probes", 4), s.get("verifier_seed", 0)
+    ok_int = lambda v: isinstance(v, int) and not isinstance(v, bool)  # noqa: E731
+    if not (ok_int(probes) and probes >= 1) and not (isinstance(probes, (list, tuple)) and probes
+                                                     and all(ok_int(r) and r >= 0 for r in probes)):
+        raise ValueError(f"search.verifier_probes = {probes!r} must be an integer >= 1 or a list of rows >= 0")
+    if not ok_int(seed) or seed < 0:
+        raise ValueError(f"search.verifier_seed = {seed!r} must be an integer >= 0")
+    try:
+        return DenoisingVerifier(sampler, mode=vname, probes=probes, seed=seed)
+    except ValueError as e:
+        raise ValueError(f"search.verifier {vname} / search.verifier_probes: {e}") from e
+
+
 def _search(cfg: Dict[str, Any], sampler, img_size: int, labels: Optional[torch.Tensor]) -> Optional[Dict[str, Any]]:
     s = cfg.get("search") or {}
     algo = (s.get("algorithm") or "none").lower()
     if algo == "none":
         return None
     from .search import SearchEngine
-    from .verifier import AestheticPredictor, OracleVerifier, SelfSupervisedVerifier
 
     vname = (s.get("verifier") or "oracle").lower()
-    ver = {"oracle": OracleVerifier, "selfsup": SelfSupervisedVerifier, "aesthetic": AestheticPredictor}[vname]()
+    ver = search_verifier(s, sampler, labels is not None)
     shape = (int(s.get("batch_per_candidate") or 1), 3, img_size, img_size)
     if vname == "selfsup" and shape[0] < 2:
         # verifier.py:243-246 averages the off-diagonal of the in-batch Gram matrix: one image

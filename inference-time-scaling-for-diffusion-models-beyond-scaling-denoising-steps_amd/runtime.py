@@ -22,6 +22,7 @@ LIB_PATH = os.environ.get("ITSD_LIB") or os.path.join(_HERE, "libitsd_hip.so")
 ITSD_OK, ITSD_ERR_INVALID, ITSD_ERR_HIP, ITSD_ERR_WEIGHTS, ITSD_ERR_NAN, ITSD_ERR_OOM, ITSD_ERR_HANDOFF = range(7)
 PREC_FP32, PREC_BF16 = 0, 1
 VERIFY_ORACLE, VERIFY_SELFSUP, VERIFY_AESTHETIC, VERIFY_MEAN = 0, 1, 2, 3
+VERIFY_DENOISE = 16  # DenoisingVerifier: scored by itsd_verify_denoise on a UNet handle, not an itsd_verify kind
 RUN_GRAPH, RUN_CLIP, RUN_SYNC = 1, 2, 4
 
 
@@ -91,6 +92,9 @@ _SIGS = {
                          ctypes.c_uint64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p],
     "itsd_sampler_predict_x0": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                 ctypes.c_float, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p],
+    "itsd_verify_denoise": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                            ctypes.c_float, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p,
+                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
     "itsd_branch": [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.c_int,
                     ctypes.c_int64, ctypes.c_float, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int64,
                     ctypes.c_void_p],
@@ -261,6 +265,28 @@ class NativeUNet:
         check(lib().itsd_sampler_predict_x0(self.h, x.data_ptr(), _ptr(labels), x.shape[0], int(t), float(a0),
                                             float(b0), out.data_ptr(), stream_ptr(x.device)))
         return out
+
+    def verify_denoise(self, x0: torch.Tensor, t: int, a: float, b: float, seed: int, stream_id: int,
+                       labels: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
+                       sse: Optional[torch.Tensor] = None, xt_out: Optional[torch.Tensor] = None,
+                       eps_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One denoising-error probe (``itsd_verify_denoise``): sse[i] = (sum (z - eps_c)^2, sum (z - eps_u)^2) of
+        x_t = a x0[i] + b z at row t, z one field for the whole batch (``noise`` [3,H,W], or Philox of (seed,
+        stream_id)). Returns sse, fp64 [n, 2] on the device; x0 is only read. xt_out / eps_out: the debug outputs."""
+        assert x0.dtype == torch.float32 and x0.is_contiguous() and x0.is_cuda
+        n = x0.shape[0]
+        if sse is None:
+            sse = torch.empty(n, 2, dtype=torch.float64, device=x0.device)
+        assert sse.dtype == torch.float64 and sse.is_contiguous() and sse.numel() == 2 * n
+        for o in (noise, xt_out, eps_out):
+            assert o is None or (o.dtype == torch.float32 and o.is_contiguous() and o.is_cuda)
+        assert noise is None or noise.numel() == x0[0].numel(), "noise is one field [3, H, W]"
+        assert xt_out is None or xt_out.numel() == x0.numel()
+        assert eps_out is None or eps_out.numel() == (2 if self.arch.cfg else 1) * x0.numel()
+        check(lib().itsd_verify_denoise(self.h, x0.data_ptr(), _ptr(labels), int(n), int(t), float(a), float(b),
+                                        int(seed) & ((1 << 64) - 1), int(stream_id) & 0xFFFFFFFF, _ptr(noise),
+                                        sse.data_ptr(), _ptr(xt_out), _ptr(eps_out), stream_ptr(x0.device)))
+        return sse
 
     def query(self, key: str) -> int:
         """itsd_unet_query: "graph_captures", "max_batch", "T_sched", "sched_form", "ws_bytes", "ops"."""

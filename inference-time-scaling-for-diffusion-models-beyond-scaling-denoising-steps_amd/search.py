@@ -147,7 +147,7 @@ class SearchEngine:
     def __init__(self, sampler, verifier, seed: int = 0, group=None, graph: bool = True, noise: str = "philox"):
         if not hasattr(verifier, "kind"):
             raise TypeError("SearchEngine needs an itsd verifier (OracleVerifier / SelfSupervisedVerifier / "
-                            "AestheticPredictor); wrap custom scorers in the sequential API")
+                            "AestheticPredictor / DenoisingVerifier); wrap custom scorers in the sequential API")
         if noise not in ("philox", "reference"):
             raise ValueError("noise must be 'philox' (sharded, counter-based) or 'reference' (parity mode)")
         self.sampler = sampler
@@ -165,11 +165,32 @@ class SearchEngine:
         if noise == "reference" and getattr(sampler, "sampler", "ddpm") != "ddpm":
             raise ValueError("noise='reference' needs the ancestral sampler: the reference has no few-step draw order")
         self.noise = noise
+        self.verifier_unet_steps = 0  # UNet evaluations a model-as-verifier spent in the current search (_score)
         self.nfes = 0  # denoise calls (candidates), as search_algorithm.py:72 counts them
         self.device = sampler.model.device
         self.best_image: Optional[torch.Tensor] = None  # denoised image of the search's best candidate
         self._best_owner = -1
         self._ref_pending: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
+
+    def _score(self, images: torch.Tensor, n_cand: int, lab: Optional[torch.Tensor]) -> torch.Tensor:
+        """This rank's scores of a round's images. A verifier that declares ``needs_context`` (``DenoisingVerifier``)
+        also receives the round's per-image labels and has its UNet evaluations counted (all ranks' images x probes);
+        every other verifier is called as it always was."""
+        if not getattr(self.verifier, "needs_context", False):
+            return self.verifier.score_batch(images, n_cand)
+        self.verifier_unet_steps += int(images.shape[0]) * self.world * int(getattr(self.verifier, "probes", 1))
+        return self.verifier.score_batch(images, n_cand, labels=lab)
+
+    def _begin_search(self) -> None:
+        self.best_image = None
+        self._best_owner = -1
+        self.verifier_unet_steps = 0
+
+    def _hist(self, hist: Dict[str, Any]) -> Dict[str, Any]:
+        """hist, plus ``verifier_unet_steps`` (images scored x probes) under a model-as-verifier."""
+        if getattr(self.verifier, "needs_context", False):
+            hist["verifier_unet_steps"] = self.verifier_unet_steps
+        return hist
 
     def reserve(self, n_candidates: int, noise_shape) -> None:
         """Size the native UNet for this rank's shard of a round up front (weights are packed
@@ -219,7 +240,7 @@ class SearchEngine:
             x = self.candidate_noise(round_id, g0, nl, shape, pivot, scale)
             self.sampler.run(x, labels=lab, seed=(self.seed * 1000003 + round_id) & ((1 << 62) - 1),
                              noise_offset=g0 * per, graph=self.graph)
-        local = self.verifier.score_batch(x, nl)
+        local = self._score(x, nl, lab)
         self.nfes += n
         if self.dist:
             parts = [torch.empty_like(local) for _ in range(self.world)]
@@ -261,21 +282,22 @@ class SearchEngine:
             dist.broadcast(self.best_image, src=src, group=self.group)
 
     # --- the three searches, batched
-    def random_search(self, n_candidates: int, noise_shape) -> Tuple[Optional[torch.Tensor], float, Dict[str, Any]]:
-        self.best_image, self._best_owner = None, -1
+    def random_search(self, n_candidates: int, noise_shape,
+                      labels=None) -> Tuple[Optional[torch.Tensor], float, Dict[str, Any]]:
+        self._begin_search()
         self.reserve(n_candidates, noise_shape)
-        r = self.run_round(0, n_candidates, noise_shape, kind="random")
+        r = self.run_round(0, n_candidates, noise_shape, labels=labels, kind="random")
         best_noise = None  # search_algorithm.py:60 (no candidate beat -inf)
         if r.best_index >= 0:
             best_noise = self._noise_of(r, 0, noise_shape)
             self._keep_best_image(r, noise_shape)
         self._publish_best_image(noise_shape)
-        return best_noise, r.best_score, {"scores": r.scores.tolist(), "best_index": r.best_index}
+        return best_noise, r.best_score, self._hist({"scores": r.scores.tolist(), "best_index": r.best_index})
 
     def zero_order_search(self, initial_noise: torch.Tensor, n_neighbors: int, lambda_radius: float,
                           n_iterations: int, labels=None):
         shape = tuple(initial_noise.shape)
-        self.best_image, self._best_owner = None, -1
+        self._begin_search()
         self.reserve(n_neighbors, shape)
         pivot = initial_noise.to(self.device, torch.float32).contiguous()
         best_noise, best_score = pivot.clone(), float("-inf")
@@ -292,12 +314,12 @@ class SearchEngine:
                 best_noise, pivot = cand.clone(), cand.clone()
                 self._keep_best_image(r, shape)
         self._publish_best_image(shape)
-        return best_noise, best_score, hist
+        return best_noise, best_score, self._hist(hist)
 
     def path_search(self, initial_noise: torch.Tensor, n_paths: int, noise_scale: float, injection_step: int = 400,
                     labels=None):
         shape = tuple(initial_noise.shape)
-        self.best_image, self._best_owner = None, -1
+        self._begin_search()
         self.reserve(n_paths, shape)
         pivot = initial_noise.to(self.device, torch.float32).contiguous()
         r = self.run_round(0, n_paths, shape, pivot=pivot, scale=noise_scale, labels=labels, kind="path")
@@ -306,8 +328,9 @@ class SearchEngine:
             best = self._noise_of(r, 0, shape, pivot=pivot, scale=noise_scale)
             self._keep_best_image(r, shape)
         self._publish_best_image(shape)
-        return best, r.best_score, {"scores": r.scores.tolist(), "injection_points": [injection_step] * n_paths,
-                                    "best_index": r.best_index}
+        return best, r.best_score, self._hist({"scores": r.scores.tolist(),
+                                               "injection_points": [injection_step] * n_paths,
+                                               "best_index": r.best_index})
 
     # --- path search that branches at the injection steps
     def window_key(self, i: int, renoise_steps: int = 0) -> int:
@@ -364,7 +387,7 @@ class SearchEngine:
         if self.noise == "reference":
             raise ValueError("the branching path search draws from Philox; noise='reference' covers the placeholder")
         shape = tuple(initial_noise.shape)
-        self.best_image, self._best_owner = None, -1
+        self._begin_search()
         self.reserve(n_paths, shape)
         g0, nl = self.shard(n_paths)
         per = int(torch.Size(shape).numel())
@@ -379,7 +402,7 @@ class SearchEngine:
                 self.sampler.run(x, t_begin=t_hi, t_end=s + 1, labels=lab, seed=self.window_key(i, delta),
                                  noise_offset=g0 * per, graph=self.graph, clip=False)
                 ran += t_hi - s
-            local = self.verifier.score_batch(self.sampler.predict_x0(x, s, labels=lab), nl)
+            local = self._score(self.sampler.predict_x0(x, s, labels=lab), nl, lab)
             sc = (self._gather(local) if self.dist else local).cpu()  # first collective of the stage
             src = self._gather(x) if self.world > 1 else x            # second: every rank holds all N latents
             tab = branch_parents(sc, keep)
@@ -391,7 +414,7 @@ class SearchEngine:
         self.sampler.run(x, t_begin=t_hi, t_end=0, labels=lab, seed=self.window_key(len(steps), delta),
                          noise_offset=g0 * per, graph=self.graph, clip=True)
         ran += t_hi + 1
-        local = self.verifier.score_batch(x, nl)
+        local = self._score(x, nl, lab)
         self.nfes += n_paths
         sc = (self._gather(local) if self.dist else local).cpu()
         best_index, best_score = strict_argmax(sc)
@@ -401,9 +424,9 @@ class SearchEngine:
             best = self.candidate_noise(0, root, 1, shape, pivot=pivot, scale=noise_scale)
             self._keep_best_image(RoundResult(sc, best_index, best_score, x, g0), shape)
         self._publish_best_image(shape)
-        return best, best_score, {"scores": sc.tolist(), "stage_scores": stage_scores, "parents": parents,
-                                  "injection_points": steps, "best_index": best_index, "root_index": root,
-                                  "unet_steps": n_paths * (ran + len(steps))}
+        return best, best_score, self._hist({"scores": sc.tolist(), "stage_scores": stage_scores, "parents": parents,
+                                             "injection_points": steps, "best_index": best_index, "root_index": root,
+                                             "unet_steps": n_paths * (ran + len(steps))})
 
 
 # --------------------------------------------------------------------------- reference API

@@ -8,7 +8,7 @@ what the batched search engine uses. CLIP-based verifiers (``verifier.py:69-188,
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Dict, List, Optional
 
 import numpy as np
 import torch
@@ -84,4 +84,93 @@ class AestheticPredictor(_NativeVerifier):
         return float(self.score_batch(images, 1)[0].item())
 
 
-VERIFIERS = {"oracle": OracleVerifier, "selfsup": SelfSupervisedVerifier, "aesthetic": AestheticPredictor}
+_STREAM_PROBE = 0xD0000000  # + probe index: the Philox stream id of a probe's noise field
+
+
+def probe_rows(n_steps: int, probes: int) -> List[int]:
+    """The default probe rows: the midpoints of ``probes`` equal parts of [0, n_steps),
+    ((2k + 1) n_steps) // (2 probes) for k < probes."""
+    n_steps, probes = int(n_steps), int(probes)
+    if probes < 1 or probes > n_steps:
+        raise ValueError(f"probes = {probes} outside [1, n_steps = {n_steps}]")
+    return [((2 * k + 1) * n_steps) // (2 * probes) for k in range(probes)]
+
+
+def combine_sse(sse: torch.Tensor, mode: str, per_image: int, n_cand: int) -> torch.Tensor:
+    """The score of each candidate from its images' per-probe error sums, in fp64. sse: [R, N, 2] (probe, image,
+    (cond, uncond)); P = per_image elements. ``denoise``: -mean_r sse_c / P; ``class``: mean_r (sse_u - sse_c) / P;
+    a candidate's score is the mean over its N // n_cand images."""
+    sse = sse.double()
+    q = -sse[:, :, 0] if mode == "denoise" else sse[:, :, 1] - sse[:, :, 0]
+    per = q.mean(dim=0) / float(per_image)
+    return per.reshape(n_cand, -1).mean(dim=1)
+
+
+class DenoisingVerifier:
+    """The diffusion model as its own verifier (no reference counterpart: every content-aware verifier of the
+    reference needs downloaded CLIP / DINO weights). A candidate image is noised back to a few rows of the sampler's
+    schedule with a known eps, the UNet predicts it, and the squared error is the score (``itsd_verify_denoise``):
+
+    * ``mode="denoise"``: minus the mean squared error under the image's label (the label-free model's own error
+      for an unconditional model) -- the per-timestep ELBO term, uniformly weighted;
+    * ``mode="class"`` (CFG models): error under the null label minus error under the label, the "diffusion
+      classifier" log-ratio: how much the label helps the model explain the image.
+
+    ``probes``: how many rows (``probe_rows(sampler.n_steps, probes)``) or an explicit list of rows. Probe r draws ONE
+    noise field for the whole batch from Philox (seed, 0xD0000000 + r), so a score is a pure function of (image,
+    label, seed, rows): not of the batch, the shard or the neighbours. Costs ``len(rows)`` UNet evaluations an image."""
+
+    kind = rt.VERIFY_DENOISE
+    needs_context = True  # SearchEngine passes the round's labels to score_batch
+
+    def __init__(self, sampler, mode: str = "denoise", probes=4, seed: int = 0):
+        if mode not in ("denoise", "class"):
+            raise ValueError(f"mode must be 'denoise' or 'class', not {mode!r}")
+        cfg = bool(getattr(getattr(sampler.model, "arch", None), "cfg", False))
+        if mode == "class" and not cfg:
+            raise ValueError("mode='class' needs a label-conditional (CFG) model: an unconditional one has no "
+                             "class ratio")
+        self.sampler, self.mode, self.seed, self.cfg = sampler, mode, int(seed), cfg
+        n_steps = int(sampler.n_steps)
+        if isinstance(probes, (list, tuple)):
+            rows = [int(r) for r in probes]
+            if not rows or any(not 0 <= r < n_steps for r in rows):
+                raise ValueError(f"probe rows {rows} must be a non-empty list inside [0, {n_steps})")
+        else:
+            rows = probe_rows(n_steps, probes)
+        self.rows = rows
+        abar = sampler.abar_rows.double()
+        # a = sqrt(abar), b = sqrt(1 - abar) of each row: fp64 here, cast to fp32 at the call
+        self.ab = [(float(torch.sqrt(abar[r])), float(torch.sqrt(1.0 - abar[r]))) for r in rows]
+
+    @property
+    def probes(self) -> int:
+        return len(self.rows)
+
+    def score_batch(self, images: torch.Tensor, n_cand: int, labels: Optional[torch.Tensor] = None) -> torch.Tensor:
+        images = _dev(images)
+        n = images.shape[0]
+        assert n % n_cand == 0, "images must split evenly into candidates"
+        if self.cfg:
+            if labels is None:
+                raise ValueError("a label-conditional (CFG) model needs labels to score")
+            labels = labels.flatten().to(images.device, torch.int32).contiguous()
+            if labels.numel() != n:
+                raise ValueError(f"{labels.numel()} labels for {n} images")
+        else:
+            labels = None
+        nat = self.sampler._native(n)
+        sse = torch.empty(len(self.rows), n, 2, dtype=torch.float64, device=images.device)
+        for r, (row, (a, b)) in enumerate(zip(self.rows, self.ab)):
+            nat.verify_denoise(images, row, a, b, self.seed, _STREAM_PROBE + r, labels=labels, sse=sse[r])
+        return combine_sse(sse, self.mode, images[0].numel(), n_cand)
+
+    def score(self, images: torch.Tensor, labels: Optional[torch.Tensor] = None) -> float:
+        return float(self.score_batch(images, 1, labels=labels)[0].item())
+
+    def __call__(self, images, labels=None, **kwargs) -> float:
+        return self.score(images, labels=labels)
+
+
+VERIFIERS = {"oracle": OracleVerifier, "selfsup": SelfSupervisedVerifier, "aesthetic": AestheticPredictor,
+             "denoise": DenoisingVerifier, "class": DenoisingVerifier}
