@@ -24,6 +24,11 @@
  *                                   verifier can score mid-trajectory: the branching PathSearch its docstring
  *                                   describes (search/search_algorithm.py:238-250; its code, :307-312, is a placeholder)
  *   itsd_branch                  <- (no reference counterpart) gather the surviving paths and re-noise them
+ *   itsd_es_candidates / _es_step / _es_workspace_bytes
+ *                                <- GradientBasedSearch (search/search_algorithm.py:343-438) without autograd: the
+ *                                   antithetic candidates pivot +- sigma z of an evolution-strategies estimate of the
+ *                                   score's gradient, and the reference's Adam step on that estimate, summed in slices
+ *                                   of kEsSlice = 16 pairs
  *   itsd_verify                  <- OracleVerifier / SelfSupervisedVerifier /
  *                                   AestheticPredictor .score (search/verifier.py:45-66,
  *                                   223-248, 262-287), batched per candidate
@@ -192,6 +197,43 @@ int itsd_branch(float* dst, const float* src, const int32_t* parents, int n_src,
  * regenerate any candidate (search_algorithm.py:67 randn, :225 pivot + randn*(1-lambda)). */
 int itsd_noise(float* out, const float* pivot, int n_cand, int64_t per_cand, float scale, uint64_t seed,
                uint32_t stream_id, int64_t cand_offset, void* stream);
+
+/* ---- The antithetic evolution-strategies gradient: GradientBasedSearch without autograd. Throughout,
+ * z_p[e] = Philox (seed, stream_id, p * per_cand + e): itsd_noise's draw for candidate p. Every fp32 expression below is
+ * evaluated without contraction in the order its parentheses state; no atomics: a call is bit-reproducible.
+ *
+ * out[j][e] = pivot[e] + (s * z_p[e]) for the global candidate c = cand_offset + j, j < n_cand: pair p = c >> 1,
+ * s = +sigma for an even c, -sigma for an odd one (pairing is by global index: a shard may begin on a minus
+ * candidate). out [n_cand][per_cand] and pivot [per_cand] are device fp32. ITSD_ERR_INVALID with a message before any
+ * HIP call: a null out / pivot, n_cand < 0, per_cand < 1, cand_offset < 0, sigma not finite or <= 0. n_cand == 0: a
+ * no-op. */
+int itsd_es_candidates(float* out, const float* pivot, int n_cand, int64_t per_cand, float sigma, uint64_t seed,
+                       uint32_t stream_id, int64_t cand_offset, void* stream);
+
+/* Bytes of the workspace itsd_es_step needs for n_pairs pairs of per_cand elements (the slice sums of the gradient,
+ * ceil(n_pairs / 16) * per_cand fp32, and one fp64 a block of the update); <= 0: invalid arguments. No device call. */
+int64_t itsd_es_workspace_bytes(int n_pairs, int64_t per_cand);
+
+/* The Adam constants of one step, computed in fp64 on the host and cast: omb1 = 1 - beta1, omb2 = 1 - beta2,
+ * c1 = lr / (1 - beta1^k), c2 = 1 / sqrt(1 - beta2^k), k = 1 for the first step. */
+typedef struct { float beta1, omb1, beta2, omb2, c1, c2, eps; } itsd_adam_step;
+
+/* One ascent step on theta [per_cand] from the weights w [n_pairs] (device fp32; for the ES estimate of the gradient
+ * of a score, w[p] = (score of candidate 2p - score of candidate 2p + 1) / (2 n_pairs sigma)):
+ *   g[e]  = sum over the slices q of (sum over the pairs p of slice q of (w[p] * z_p[e]))
+ *           slice q = pairs [kEsSlice q, min(n_pairs, kEsSlice (q + 1))), kEsSlice = 16 (csrc/common.h); both sums
+ *           ascend and start from 0.0f; a pair with w[p] == 0 is not drawn
+ *   gl = -g;  m' = (beta1 m) + (omb1 gl);  v' = (beta2 v) + (omb2 (gl gl));
+ *   den = (sqrtf(v') c2) + eps;  theta' = theta - ((c1 m') / den)
+ * theta, m, v are updated in place (torch.optim.Adam's step on grad = -g: it ascends g). grad_out (NULL ok) receives
+ * g; gnorm2_out (device fp64 [1]) the sum of g^2 in fp64: every block of the update adds its elements in a fixed order
+ * and a last launch adds the blocks in block order. ws: itsd_es_workspace_bytes(n_pairs, per_cand) bytes of device
+ * memory, 16-byte aligned, overwritten. ITSD_ERR_INVALID with a message before any HIP call: a null theta / m / v / w /
+ * adam / gnorm2_out / ws, n_pairs < 1, per_cand < 1, beta1 or beta2 outside [0, 1), eps <= 0, a non-finite field of
+ * adam, a misaligned ws, or any two of theta / m / v / grad_out / ws overlapping. */
+int itsd_es_step(float* theta, float* m, float* v, const float* w, int n_pairs, int64_t per_cand, uint64_t seed,
+                 uint32_t stream_id, const itsd_adam_step* adam, float* grad_out, double* gnorm2_out, void* ws,
+                 void* stream);
 
 /* scores[c] = verifier(images[c*b:(c+1)*b]) for c < n_cand; images NCHW fp32.
  * ITSD_VERIFY_MEAN is OracleVerifier.score with dataset_stats (search/verifier.py:66: mean). */

@@ -60,6 +60,12 @@ hipError_t launch_branch(float*, const float*, const int*, int, long long, float
                          long long, hipStream_t);
 hipError_t launch_probe_noise(float*, const float*, const float*, int, long long, float, float, unsigned long long,
                               unsigned, hipStream_t);
+hipError_t launch_es_candidates(float*, const float*, int, long long, float, unsigned long long, unsigned, long long,
+                                hipStream_t);
+long long es_blocks(long long per_cand);
+long long es_workspace_bytes(int n_pairs, long long per_cand);
+hipError_t launch_es_step(float*, float*, float*, const float*, int, long long, unsigned long long, unsigned,
+                          const EsAdam&, float*, double*, void*, hipStream_t);
 template <typename T> hipError_t launch_nhwc_to_nchw(const void*, float*, int, int, int, hipStream_t);
 }  // namespace itsd
 
@@ -1956,6 +1962,60 @@ int itsd_noise(float* out, const float* pivot, int n_cand, int64_t per_cand, flo
   if (!out || n_cand < 0 || per_cand < 1) return fail(ITSD_ERR_INVALID, "bad noise arguments");
   if (n_cand == 0) return ITSD_OK;
   HIPCHK(launch_noise(out, pivot, n_cand, per_cand, scale, seed, stream_id, cand_offset, (hipStream_t)stream));
+  return ITSD_OK;
+}
+
+namespace {
+constexpr int64_t kEsMaxPer = (int64_t)1 << 40;  // es_adam_kernel's blocks fit gridDim.x, the workspace size an int64
+bool es_sizes_ok(int n_pairs, int64_t per_cand) {
+  return n_pairs >= 1 && n_pairs <= kEsMaxPairs && per_cand >= 1 && per_cand <= kEsMaxPer;
+}
+}  // namespace
+
+int64_t itsd_es_workspace_bytes(int n_pairs, int64_t per_cand) {
+  return es_sizes_ok(n_pairs, per_cand) ? (int64_t)es_workspace_bytes(n_pairs, per_cand) : 0;
+}
+
+int itsd_es_candidates(float* out, const float* pivot, int n_cand, int64_t per_cand, float sigma, uint64_t seed,
+                       uint32_t stream_id, int64_t cand_offset, void* stream) {
+  if (!out || !pivot) return fail(ITSD_ERR_INVALID, "itsd_es_candidates: null argument");
+  if (n_cand < 0 || per_cand < 1 || per_cand > kEsMaxPer || cand_offset < 0)
+    return fail(ITSD_ERR_INVALID, "itsd_es_candidates: needs n_cand >= 0, 1 <= per_cand <= 2^40, cand_offset >= 0");
+  if (!std::isfinite(sigma) || sigma <= 0.0f)
+    return fail(ITSD_ERR_INVALID, "itsd_es_candidates: sigma must be finite and > 0");
+  if (n_cand == 0) return ITSD_OK;
+  HIPCHK(launch_es_candidates(out, pivot, n_cand, per_cand, sigma, seed, stream_id, cand_offset, (hipStream_t)stream));
+  return ITSD_OK;
+}
+
+int itsd_es_step(float* theta, float* m, float* v, const float* w, int n_pairs, int64_t per_cand, uint64_t seed,
+                 uint32_t stream_id, const itsd_adam_step* adam, float* grad_out, double* gnorm2_out, void* ws,
+                 void* stream) {
+  if (!theta || !m || !v || !w || !adam || !gnorm2_out || !ws)
+    return fail(ITSD_ERR_INVALID, "itsd_es_step: null argument");
+  if (!es_sizes_ok(n_pairs, per_cand))
+    return fail(ITSD_ERR_INVALID, "itsd_es_step: needs 1 <= n_pairs <= " + std::to_string(kEsMaxPairs) +
+                                      ", 1 <= per_cand <= 2^40");
+  if ((uintptr_t)ws % 16) return fail(ITSD_ERR_INVALID, "itsd_es_step: ws must be 16-byte aligned");
+  const float f[7] = {adam->beta1, adam->omb1, adam->beta2, adam->omb2, adam->c1, adam->c2, adam->eps};
+  for (float x : f)
+    if (!std::isfinite(x)) return fail(ITSD_ERR_INVALID, "itsd_es_step: a field of adam is not finite");
+  if (adam->beta1 < 0.0f || adam->beta1 >= 1.0f || adam->beta2 < 0.0f || adam->beta2 >= 1.0f)
+    return fail(ITSD_ERR_INVALID, "itsd_es_step: adam beta1 / beta2 must lie in [0, 1)");
+  if (adam->eps <= 0.0f) return fail(ITSD_ERR_INVALID, "itsd_es_step: adam eps must be > 0");
+  {
+    const uintptr_t eb = (uintptr_t)per_cand * 4;
+    const struct { const char* name; uintptr_t p, bytes; } r[5] = {
+        {"theta", (uintptr_t)theta, eb}, {"m", (uintptr_t)m, eb}, {"v", (uintptr_t)v, eb},
+        {"grad_out", (uintptr_t)grad_out, eb}, {"ws", (uintptr_t)ws, (uintptr_t)es_workspace_bytes(n_pairs, per_cand)}};
+    for (int i = 0; i < 5; ++i)
+      for (int j = i + 1; j < 5; ++j)
+        if (r[i].p && r[j].p && r[i].p < r[j].p + r[j].bytes && r[j].p < r[i].p + r[i].bytes)
+          return fail(ITSD_ERR_INVALID, std::string("itsd_es_step: ") + r[i].name + " and " + r[j].name + " overlap");
+  }
+  const EsAdam a{adam->beta1, adam->omb1, adam->beta2, adam->omb2, adam->c1, adam->c2, adam->eps};
+  HIPCHK(launch_es_step(theta, m, v, w, n_pairs, per_cand, seed, stream_id, a, grad_out, gnorm2_out, ws,
+                        (hipStream_t)stream));
   return ITSD_OK;
 }
 

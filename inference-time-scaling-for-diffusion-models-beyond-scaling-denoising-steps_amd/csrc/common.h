@@ -355,4 +355,13 @@ struct TailArgs {
 
 constexpr int kBranchChunk = 256;  // parent-table rows a branch_kernel launch carries in its arguments (1 KiB)
 
+// The antithetic ES gradient (itsd_es_step): pairs a slice of es_grad_kernel sums, in ascending order, before
+// es_adam_kernel adds the slices in slice order. It defines the summation order of the gradient (include/itsd.h names
+// it), and so the rounding bound the tests assert. kEsItems: elements a thread of es_adam_kernel updates, so a block
+// covers 256 * kEsItems elements and stores one fp64 partial of |g|^2.
+constexpr int kEsSlice = 16;
+constexpr int kEsItems = 4;
+constexpr int kEsMaxPairs = kEsSlice * 65535;  // slices ride on gridDim.y
+struct EsAdam { float beta1, omb1, beta2, omb2, c1, c2, eps; };  // itsd_adam_step (include/itsd.h), field for field
+
 }  // namespace itsd

@@ -2289,6 +2289,158 @@ hipError_t launch_branch(float* dst, const float* src, const int* parents, int n
   return hipSuccess;
 }
 
+// ---- the antithetic evolution-strategies gradient (itsd_es_candidates / itsd_es_step). Throughout,
+// z_p[e] = Philox (seed, stream_id, p * per_cand + e): noise_kernel's draw for candidate p. All fp32 arithmetic is
+// written without contraction, in the order stated, so the tests can demand bits.
+//
+// out[j][e] = pivot[e] + (s * z_p[e]) for the global candidate c = cand0 + j: pair p = c >> 1, s = +sigma for an even
+// c and -sigma for an odd one (pairing is by GLOBAL index: a shard may start on a minus candidate). grid = (element
+// blocks, rows); VEC as branch_kernel's.
+template <bool VEC>
+__global__ __launch_bounds__(256) void es_candidates_kernel(float* out, const float* pivot, long long per_cand,
+                                                            float sigma, unsigned long long seed, unsigned stream_id,
+                                                            long long cand0) {
+#pragma clang fp contract(off)
+  const long long j = blockIdx.y, c = cand0 + j;
+  const float s = (c & 1) ? -sigma : sigma;
+  float* op = out + j * per_cand;
+  const unsigned long long zb = (unsigned long long)(c >> 1) * (unsigned long long)per_cand;
+  const long long stride = (long long)gridDim.x * 256;
+  if constexpr (VEC) {
+    const long long nv = per_cand >> 2;
+    for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < nv; v += stride) {
+      const f32x4 p4 = *(const f32x4*)(pivot + 4 * v);
+      f32x4 o;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float sz = s * philox_normal(seed, stream_id, zb + (unsigned long long)(4 * v + e));
+        o[e] = p4[e] + sz;
+      }
+      *(f32x4*)(op + 4 * v) = o;
+    }
+  } else {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < per_cand; i += stride) {
+      const float sz = s * philox_normal(seed, stream_id, zb + (unsigned long long)i);
+      op[i] = pivot[i] + sz;
+    }
+  }
+}
+hipError_t launch_es_candidates(float* out, const float* pivot, int n_cand, long long per_cand, float sigma,
+                                unsigned long long seed, unsigned stream_id, long long cand_offset, hipStream_t s) {
+  const bool vec = per_cand % 4 == 0 && ((uintptr_t)out | (uintptr_t)pivot) % 16 == 0;
+  const long long items = vec ? per_cand / 4 : per_cand;
+  const unsigned gx = (unsigned)std::min<long long>((items + 255) / 256, 1 << 16);
+  constexpr int kRows = 65535;  // gridDim.y
+  for (int j0 = 0; j0 < n_cand; j0 += kRows) {
+    const int rows = std::min(kRows, n_cand - j0);
+    float* o = out + (long long)j0 * per_cand;
+    if (vec) ITSD_LAUNCH(es_candidates_kernel<true>, dim3(gx, rows), dim3(256), 0, s, o, pivot, per_cand, sigma, seed,
+                         stream_id, cand_offset + j0);
+    else ITSD_LAUNCH(es_candidates_kernel<false>, dim3(gx, rows), dim3(256), 0, s, o, pivot, per_cand, sigma, seed,
+                     stream_id, cand_offset + j0);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// part[q][e] = sum over the pairs p of slice q, [kEsSlice q, min(n_pairs, kEsSlice (q + 1))), ascending from 0.0f, of
+// (w[p] * z_p[e]); one plain store. grid = (element blocks, slices): the draws of n_pairs normals an element spread
+// over the chip instead of running as one loop a thread. w is wave-uniform (scalar loads); a pair with w[p] == 0 adds
+// a zero of either sign to a sum that started at +0 and skips its draw (the bits are the same).
+__global__ __launch_bounds__(256) void es_grad_kernel(float* part, const float* __restrict__ w, int n_pairs,
+                                                      long long per_cand, unsigned long long seed,
+                                                      unsigned stream_id) {
+#pragma clang fp contract(off)
+  const int q = blockIdx.y, p0 = q * kEsSlice, p1 = p0 + kEsSlice < n_pairs ? p0 + kEsSlice : n_pairs;
+  float* dp = part + (long long)q * per_cand;
+  const long long stride = (long long)gridDim.x * 256;
+  for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < per_cand; e += stride) {
+    float acc = 0.0f;
+    for (int p = p0; p < p1; ++p) {
+      const float wp = w[p];
+      if (wp != 0.0f) {
+        const float wz = wp * philox_normal(seed, stream_id,
+                                            (unsigned long long)p * (unsigned long long)per_cand + (unsigned long long)e);
+        acc = acc + wz;
+      }
+    }
+    dp[e] = acc;
+  }
+}
+
+// g[e] = sum over the nq slices, ascending from 0.0f, of part[q][e]; then the Adam ascent step of itsd_es_step on
+// theta, m, v in place (the optimiser descends on gl = -g). A thread owns the elements base + 256 k + tid, k <
+// kEsItems, of its block's 256 kEsItems. The block also adds its g^2 in fp64 in a fixed order -- the thread's items in
+// order, a lane butterfly, the wave partials in wave order by thread 0 -- and stores the sum to bpart[blockIdx.x].
+__global__ __launch_bounds__(256) void es_adam_kernel(float* theta, float* m, float* v, const float* __restrict__ part,
+                                                      int nq, long long per_cand, EsAdam a, float* grad_out,
+                                                      double* bpart) {
+#pragma clang fp contract(off)
+  __shared__ double wsum[4];
+  const long long base = (long long)blockIdx.x * (256 * kEsItems);
+  double acc = 0.0;
+#pragma unroll
+  for (int k = 0; k < kEsItems; ++k) {
+    const long long e = base + k * 256 + threadIdx.x;
+    if (e < per_cand) {
+      float g = 0.0f;
+      for (int q = 0; q < nq; ++q) g = g + part[(long long)q * per_cand + e];
+      if (grad_out) grad_out[e] = g;
+      const float gl = -g;
+      const float m1 = (a.beta1 * m[e]) + (a.omb1 * gl);
+      const float v1 = (a.beta2 * v[e]) + (a.omb2 * (gl * gl));
+      const float den = (sqrtf(v1) * a.c2) + a.eps;
+      theta[e] = theta[e] - ((a.c1 * m1) / den);
+      m[e] = m1;
+      v[e] = v1;
+      acc += (double)g * (double)g;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) bpart[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+}
+
+// gnorm2[0] = the block partials of es_adam_kernel, added in block order in fp64
+__global__ __launch_bounds__(64) void es_norm_finalize_kernel(const double* bpart, long long nb, double* gnorm2) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  double s = 0.0;
+  for (long long b = 0; b < nb; ++b) s += bpart[b];
+  gnorm2[0] = s;
+}
+
+// One ES update: the two-level gradient into part (ws), the Adam step, the norm. bpart follows part in ws
+// (es_workspace_bytes is the layout's one statement).
+long long es_part_bytes(int n_pairs, long long per_cand) {
+  const long long nq = (n_pairs + kEsSlice - 1) / kEsSlice;
+  return (nq * per_cand * 4 + 15) / 16 * 16;
+}
+long long es_blocks(long long per_cand) { return (per_cand + 256 * kEsItems - 1) / (256 * kEsItems); }
+long long es_workspace_bytes(int n_pairs, long long per_cand) {
+  return es_part_bytes(n_pairs, per_cand) + es_blocks(per_cand) * 8;
+}
+hipError_t launch_es_step(float* theta, float* m, float* v, const float* w, int n_pairs, long long per_cand,
+                          unsigned long long seed, unsigned stream_id, const EsAdam& adam, float* grad_out,
+                          double* gnorm2, void* ws, hipStream_t s) {
+  float* part = (float*)ws;
+  double* bpart = (double*)((char*)ws + es_part_bytes(n_pairs, per_cand));
+  const int nq = (n_pairs + kEsSlice - 1) / kEsSlice;
+  const long long nb = es_blocks(per_cand);
+  const unsigned gx = (unsigned)std::min<long long>((per_cand + 255) / 256, 1 << 20);
+  ITSD_LAUNCH(es_grad_kernel, dim3(gx, nq), dim3(256), 0, s, part, w, n_pairs, per_cand, seed, stream_id);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  ITSD_LAUNCH(es_adam_kernel, dim3((unsigned)nb), dim3(256), 0, s, theta, m, v, part, nq, per_cand, adam, grad_out,
+              bpart);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  ITSD_LAUNCH(es_norm_finalize_kernel, dim3(1), dim3(64), 0, s, bpart, nb, gnorm2);
+  return hipGetLastError();
+}
+
 // The probe noising of itsd_verify_denoise: xt[i][e] = (a x0[i][e]) + (b z[e]) for i < n, e < per, fp32 without
 // contraction, z[e] = noise[e] or Philox (seed, stream_id, e): ONE field, indexed by the element within the image and
 // shared by every image (the draw tail_sse_item repeats). grid = (element blocks, groups of kProbeImgs images: the

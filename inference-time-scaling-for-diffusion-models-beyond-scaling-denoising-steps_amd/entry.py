@@ -22,7 +22,7 @@ Keys beyond the reference (all optional):
   run batched (and sharded over ranks when launched with torchrun) by ``itsd.search.SearchEngine``::
 
       search:
-        algorithm: random        # random | zero_order | path | none
+        algorithm: random        # random | zero_order | path | gradient | none
         n_candidates: 256        # random
         n_neighbors: 4           # zero_order
         lambda_radius: 0.95
@@ -30,11 +30,19 @@ Keys beyond the reference (all optional):
         n_paths: 4               # path
         injection_step: 400
         noise_scale: 0.1
+        n_pairs: 4               # gradient: antithetic pairs an iteration (2 n_pairs candidates)
+        sigma: 0.05              # gradient: the perturbation radius of the ES estimate
+        lr: 0.01                 # gradient: Adam's learning rate (n_iterations defaults to 20 here)
+        shaping: raw             # gradient: raw | rank (scores, or their centred ranks)
         verifier: oracle         # oracle | selfsup | aesthetic | denoise | class
         verifier_probes: 4       # denoise / class: UNet evaluations an image (rows spread over the sampler's
                                  # schedule), or an explicit list of rows
         verifier_seed: 0         # denoise / class: Philox key of the probes' noise fields
         bestImgName: SearchBestImgs.png
+
+  ``gradient`` is ``GradientBasedSearch`` without autograd (``SearchEngine.gradient_search``):
+  an evolution-strategies estimate of the score's gradient from antithetic candidates, stepped by Adam; it is
+  label-aware like ``zero_order`` and pairs best with a deterministic sampler (``sampler: {kind: ddim, eta: 0}``).
 
   ``denoise`` and ``class`` score with the diffusion model itself (``itsd.verifier.DenoisingVerifier``, no reference
   counterpart: the reference's content-aware verifiers need downloaded CLIP / DINO weights): the squared error of the
@@ -492,6 +500,11 @@ def _search(cfg: Dict[str, Any], sampler, img_size: int, labels: Optional[torch.
             best, score, hist = eng.zero_order_search(init, int(s.get("n_neighbors") or 4),
                                                       float(s.get("lambda_radius", 0.95)),
                                                       int(s.get("n_iterations") or 10), labels=lab)
+        elif algo == "gradient":
+            n_it = s.get("n_iterations")
+            best, score, hist = eng.gradient_search(init, int(s.get("n_pairs") or 4), float(s.get("sigma", 0.05)),
+                                                    20 if n_it is None else int(n_it), lr=float(s.get("lr", 0.01)),
+                                                    shaping=str(s.get("shaping") or "raw").lower(), labels=lab)
         elif algo == "path":
             mode = (s.get("path_mode") or "placeholder").lower()
             n_paths, inj = int(s.get("n_paths") or 4), s.get("injection_step") or 400

@@ -14,6 +14,7 @@ from typing import Dict, Optional, Sequence
 import torch
 
 from .arch import ARCH_CFG, ARCH_DDPM, UNetArch
+from .schedule import adam_coeffs  # noqa: F401  (es_step's ``adam`` argument)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # ITSD_LIB: an alternative build of the same library (diagnostic A/B builds under build_diag/)
@@ -51,6 +52,11 @@ class X0Schedule(ctypes.Structure):
 
 
 X0_ROW_KEYS = ("a0", "b0", "c0", "cx", "sg")
+
+
+class AdamStep(ctypes.Structure):
+    """itsd_adam_step (include/itsd.h): one step's constants (``schedule.adam_coeffs``)."""
+    _fields_ = [(k, ctypes.c_float) for k in ("beta1", "omb1", "beta2", "omb2", "c1", "c2", "eps")]
 
 
 class OpInfo(ctypes.Structure):
@@ -100,6 +106,11 @@ _SIGS = {
                     ctypes.c_void_p],
     "itsd_noise": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_uint64,
                    ctypes.c_uint32, ctypes.c_int64, ctypes.c_void_p],
+    "itsd_es_candidates": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float,
+                           ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int64, ctypes.c_void_p],
+    "itsd_es_step": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
+                     ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(AdamStep), ctypes.c_void_p, ctypes.c_void_p,
+                     ctypes.c_void_p, ctypes.c_void_p],
     "itsd_verify": [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                     ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p],
     "itsd_verify_paired": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
@@ -127,7 +138,14 @@ _SIGS = {
     "itsd_version": [],
 }
 
+# entry points that return an int64_t size, not a status. EXPORTS stays the list of the header's status- and
+# string-returning functions (what tests/test_lib_cpu.py reads out of include/itsd.h); these are bound beside them
+_SIGS_I64 = {
+    "itsd_es_workspace_bytes": [ctypes.c_int, ctypes.c_int64],
+}
+
 EXPORTS = tuple(_SIGS)
+EXPORTS_I64 = tuple(_SIGS_I64)
 
 
 def lib():
@@ -138,12 +156,13 @@ def lib():
             raise ItsdError(ITSD_ERR_INVALID, f"{LIB_PATH} is not built; run __graft_entry__.build()")
         L = ctypes.CDLL(LIB_PATH)
         shipped = os.path.abspath(LIB_PATH) == os.path.join(_HERE, "libitsd_hip.so")
-        for name, args in _SIGS.items():
+        for name, args in {**_SIGS, **_SIGS_I64}.items():
             if not shipped and not hasattr(L, name):
                 continue  # (an older build loaded for an A/B measurement: entry points it predates are absent)
             f = getattr(L, name)
             f.argtypes = args
-            f.restype = ctypes.c_char_p if name in ("itsd_last_error", "itsd_kernel_name") else ctypes.c_int
+            f.restype = (ctypes.c_char_p if name in ("itsd_last_error", "itsd_kernel_name") else
+                         ctypes.c_int64 if name in _SIGS_I64 else ctypes.c_int)
         _lib = L
     return _lib
 
@@ -413,6 +432,49 @@ def branch(dst: torch.Tensor, src: torch.Tensor, parents: Sequence[int], a: floa
                             int(seed) & ((1 << 64) - 1), int(stream_id) & 0xFFFFFFFF, int(cand_offset),
                             stream_ptr(dst.device)))
     return dst
+
+
+def es_candidates(out: torch.Tensor, pivot: torch.Tensor, n_cand: int, sigma: float, seed: int, stream_id: int,
+                  cand_offset: int = 0) -> torch.Tensor:
+    """out[j] = pivot + (s * z_p) for the global candidate c = cand_offset + j: pair p = c >> 1, s = +sigma (even c) or
+    -sigma (odd c), z_p the draw ``noise`` makes for candidate p of (seed, stream_id) (``itsd_es_candidates``)."""
+    assert out.dtype == torch.float32 and pivot.dtype == torch.float32 and out.is_contiguous() and pivot.is_contiguous()
+    per = pivot.numel()
+    assert out.numel() == int(n_cand) * per, "out is [n_cand] pivots"
+    check(lib().itsd_es_candidates(out.data_ptr(), pivot.data_ptr(), int(n_cand), int(per), float(sigma),
+                                   int(seed) & ((1 << 64) - 1), int(stream_id) & 0xFFFFFFFF, int(cand_offset),
+                                   stream_ptr(out.device)))
+    return out
+
+
+def es_workspace_bytes(n_pairs: int, per_cand: int) -> int:
+    """Bytes of ``es_step``'s workspace (``itsd_es_workspace_bytes``; no device call)."""
+    n = int(lib().itsd_es_workspace_bytes(int(n_pairs), int(per_cand)))
+    if n <= 0:
+        raise ItsdError(ITSD_ERR_INVALID, f"itsd_es_workspace_bytes: invalid n_pairs={n_pairs}, per_cand={per_cand}")
+    return n
+
+
+def es_step(theta: torch.Tensor, m: torch.Tensor, v: torch.Tensor, w: torch.Tensor, seed: int, stream_id: int,
+            adam: Dict[str, float], ws: torch.Tensor, grad_out: Optional[torch.Tensor] = None,
+            gnorm2: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One Adam ascent step on theta (m, v: its moments; all updated in place) along g = sum_p w[p] z_p, z_p the draws
+    of ``es_candidates`` under the same (seed, stream_id) (``itsd_es_step``). ``adam``: ``schedule.adam_coeffs`` of this
+    step; ``ws``: ``es_workspace_bytes(len(w), theta.numel())`` bytes of device memory. Returns the device fp64 [1]
+    tensor holding |g|^2 (``gnorm2``, or a new one); ``grad_out`` receives g."""
+    for t in (theta, m, v, w, grad_out):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous())
+    per, n_pairs = theta.numel(), w.numel()
+    assert m.numel() == per and v.numel() == per and (grad_out is None or grad_out.numel() == per)
+    assert ws.is_contiguous() and ws.numel() * ws.element_size() >= es_workspace_bytes(n_pairs, per), "ws too small"
+    if gnorm2 is None:
+        gnorm2 = torch.empty(1, dtype=torch.float64, device=theta.device)
+    assert gnorm2.dtype == torch.float64 and gnorm2.numel() == 1
+    a = AdamStep(*[float(adam[k]) for k, _ in AdamStep._fields_])
+    check(lib().itsd_es_step(theta.data_ptr(), m.data_ptr(), v.data_ptr(), w.data_ptr(), int(n_pairs), int(per),
+                             int(seed) & ((1 << 64) - 1), int(stream_id) & 0xFFFFFFFF, ctypes.byref(a),
+                             _ptr(grad_out), gnorm2.data_ptr(), ws.data_ptr(), stream_ptr(theta.device)))
+    return gnorm2
 
 
 CALIB_MFMA_BF16, CALIB_HBM_COPY, CALIB_MFMA_BF16_16X16 = 0, 1, 2

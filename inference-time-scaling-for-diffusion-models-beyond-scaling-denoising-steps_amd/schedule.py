@@ -72,6 +72,21 @@ def renoise_coeffs(alphas_bar: torch.Tensor, s: int, delta: int) -> Tuple[float,
     return math.sqrt(r), math.sqrt(1.0 - r)
 
 
+def adam_coeffs(lr: float, betas: Tuple[float, float], eps: float, k: int) -> Dict[str, float]:
+    """The constants of Adam's step k >= 1 as ``itsd_es_step`` takes them (``itsd_adam_step``), in fp64 (the device
+    consumes their fp32 casts): omb1 = 1 - beta1, omb2 = 1 - beta2, c1 = lr / (1 - beta1^k), c2 = 1 / sqrt(1 - beta2^k).
+    With them theta' = theta - (c1 m') / (sqrt(v') c2 + eps) is ``torch.optim.Adam``'s update."""
+    b1, b2, k = float(betas[0]), float(betas[1]), int(k)
+    if k < 1:
+        raise ValueError("Adam steps count from k = 1")
+    if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+        raise ValueError(f"betas = {betas!r} must lie in [0, 1)")
+    if not (lr > 0.0 and eps > 0.0):
+        raise ValueError("lr and eps must be > 0")
+    return {"beta1": b1, "omb1": 1.0 - b1, "beta2": b2, "omb2": 1.0 - b2, "c1": float(lr) / (1.0 - b1 ** k),
+            "c2": 1.0 / math.sqrt(1.0 - b2 ** k), "eps": float(eps)}
+
+
 def strided_timesteps(T: int, K: int) -> List[int]:
     """The default row -> timestep map of a K-row sampler over a T-step schedule: tau[k] = ((k + 1) T) // K - 1.
     Strictly increasing, tau[K - 1] = T - 1, and K = T is the identity."""

@@ -2,10 +2,11 @@
 
 Two layers:
 
-1. ``RandomSearch`` / ``ZeroOrderSearch`` / ``PathSearch`` keep the reference
+1. ``RandomSearch`` / ``ZeroOrderSearch`` / ``PathSearch`` / ``GradientBasedSearch`` keep the reference
    constructors, ``search`` signatures, return values, ``nfes`` bookkeeping and the
    sequential candidate loop, calling the user's ``denoise_fn`` / ``verifier_fn``
-   (``search_algorithm.py:18-340``). With ``batched=True`` (and a ``sampler=`` plus an
+   (``search_algorithm.py:18-438``; the gradient search estimates its gradient from scores,
+   without autograd). With ``batched=True`` (and a ``sampler=`` plus an
    itsd verifier) a round's candidates are instead denoised as ONE batch.
 
 2. ``SearchEngine`` is the MI355X-native round executor: the round's N candidates
@@ -35,12 +36,13 @@ import torch
 import torch.distributed as dist
 
 from . import runtime as rt
-from .schedule import renoise_coeffs
+from .schedule import adam_coeffs, renoise_coeffs
 
 _STREAM_XT = 0xF0000000      # Philox stream ids (the sampler uses stream id = t < T)
 _STREAM_PERTURB = 0xE0000000
 _STREAM_INIT = 0xD0000000    # the initial pivot of zero-order / path search
 _STREAM_BRANCH = 0xC0000000  # + stage index: the re-noising draws of a branching path search
+_STREAM_ES = 0xB0000000      # + round id: the pair draws z_p of a gradient search's iteration
 _ROUND_BRANCH = 0x5B000000   # + window index (>= 1): the sampler keys of the windows after a branch
 
 
@@ -80,6 +82,32 @@ def root_of(parents: Sequence[Sequence[int]], index: int) -> int:
             break
         index = tab[index]
     return index
+
+
+ES_SHAPINGS = ("raw", "rank")
+
+
+def es_weights(scores, sigma: float, shaping: str = "raw") -> torch.Tensor:
+    """The pair weights of the antithetic ES gradient estimate g = sum_p w_p z_p from the 2M scores of the candidates
+    theta + sigma z_p (index 2p) and theta - sigma z_p (index 2p + 1): w_p = (s[2p] - s[2p+1]) / (2 M sigma), in fp64,
+    returned as fp32 [M] on the CPU. A pair whose difference is not finite gets 0, so a NaN score never steers.
+    shaping="rank" first replaces the scores by centred ranks u_c = 0.5 - r_c / (2M - 1), r_c the candidate's place in
+    ``rank_desc`` (ties go to the lower index, NaN last): the step then depends on the order of the scores only."""
+    if shaping not in ES_SHAPINGS:
+        raise ValueError(f"shaping must be one of {ES_SHAPINGS}")
+    if not sigma > 0:
+        raise ValueError("sigma must be > 0")
+    s = torch.as_tensor(scores).detach().double().cpu().flatten()
+    n = s.numel()
+    if n < 2 or n % 2:
+        raise ValueError("es_weights needs the scores of M >= 1 antithetic pairs (2M values)")
+    if shaping == "rank":
+        u = torch.empty(n, dtype=torch.float64)
+        for place, c in enumerate(rank_desc(s)):
+            u[c] = 0.5 - place / (n - 1)
+        s = u
+    d = ((s[0::2] - s[1::2]) / (n * float(sigma))).float()
+    return torch.where(torch.isfinite(d), d, torch.zeros_like(d))
 
 
 # --------------------------------------------------------------------------- engine
@@ -238,8 +266,17 @@ class SearchEngine:
             self.sampler.run(x, labels=lab, noise=z_cpu, graph=self.graph)
         else:
             x = self.candidate_noise(round_id, g0, nl, shape, pivot, scale)
-            self.sampler.run(x, labels=lab, seed=(self.seed * 1000003 + round_id) & ((1 << 62) - 1),
-                             noise_offset=g0 * per, graph=self.graph)
+            self._denoise(round_id, x, g0, per, lab)
+        return self._finish_round(x, n, nl, g0, lab)
+
+    def _denoise(self, round_id: int, x: torch.Tensor, g0: int, per: int, lab: Optional[torch.Tensor]) -> None:
+        """A Philox round's sampler run, in place on this rank's candidates x: keyed by (seed, round) and the
+        candidates' global element positions."""
+        self.sampler.run(x, labels=lab, seed=(self.seed * 1000003 + round_id) & ((1 << 62) - 1),
+                         noise_offset=g0 * per, graph=self.graph)
+
+    def _finish_round(self, x: torch.Tensor, n: int, nl: int, g0: int, lab: Optional[torch.Tensor]) -> RoundResult:
+        """Score this rank's denoised candidates, gather the round's n scores, pick the winner."""
         local = self._score(x, nl, lab)
         self.nfes += n
         if self.dist:
@@ -331,6 +368,83 @@ class SearchEngine:
         return best, r.best_score, self._hist({"scores": r.scores.tolist(),
                                                "injection_points": [injection_step] * n_paths,
                                                "best_index": r.best_index})
+
+    # --- gradient search without autograd: an antithetic ES estimate of the score's gradient, stepped by Adam
+    def es_candidates(self, round_id: int, g0: int, count: int, shape, pivot: torch.Tensor,
+                      sigma: float) -> torch.Tensor:
+        """x_T of the antithetic candidates g0..g0+count-1 of pivot theta: theta + sigma z_p for the even global index
+        2p, theta - sigma z_p for 2p + 1 (``itsd_es_candidates``; a pure function of the global index)."""
+        out = torch.empty((count * shape[0],) + tuple(shape[1:]), dtype=torch.float32, device=self.device)
+        return rt.es_candidates(out, pivot, count, sigma, self.seed, _STREAM_ES + round_id, cand_offset=g0)
+
+    def es_workspace(self, n_pairs: int, per: int) -> Optional[torch.Tensor]:
+        """The scratch ``es_update`` needs, allocated once a search."""
+        return torch.empty(rt.es_workspace_bytes(n_pairs, per), dtype=torch.uint8, device=self.device)
+
+    def es_update(self, round_id: int, theta: torch.Tensor, m: torch.Tensor, v: torch.Tensor, w: torch.Tensor,
+                  adam: Dict[str, float], ws: Optional[torch.Tensor], gnorm2: torch.Tensor) -> None:
+        """One Adam ascent step on theta (moments m, v; all in place) along g = sum_p w[p] z_p, z_p the round's own
+        draws; gnorm2 (fp64 [1]) receives |g|^2 (``itsd_es_step``). Every rank runs the same update on the same
+        inputs, so the pivots never diverge and none crosses the fabric."""
+        rt.es_step(theta, m, v, w, self.seed, _STREAM_ES + round_id, adam, ws, gnorm2=gnorm2)
+
+    def gradient_search(self, initial_noise: torch.Tensor, n_pairs: int, sigma: float, n_iterations: int,
+                        lr: float = 0.01, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
+                        shaping: str = "raw", labels=None):
+        """``GradientBasedSearch`` (``search_algorithm.py:343-438``) for any verifier: no back-propagation through the
+        sampler. Iteration it (Adam step k = it + 1) denoises and scores the N = 2 n_pairs antithetic candidates
+        theta +- sigma z_p as one sharded round (``run_round``'s keys, one all_gather), turns the score differences
+        into the ES estimate g = sum_p w_p z_p (``es_weights``) and takes the reference's optimiser step on
+        grad = -g. The reference tracks the best iterate; the iterate itself is never denoised here, so the best
+        EVALUATED candidate is tracked: best_noise is its x_T (regenerated from the pre-update theta and its global
+        index) and ``best_image`` its image.
+
+        Returns (best_noise, best_score, hist); hist: ``scores`` [it][N], ``grad_norms`` (|g|_2), ``best_index``,
+        ``candidates_per_iter``, ``pivot_rms`` (sqrt(mean theta^2) after each step: the drift off the unit shell)."""
+        n_pairs = int(n_pairs)
+        if n_pairs < 1:
+            raise ValueError("n_pairs must be >= 1")
+        if not float(sigma) > 0 or float(sigma) == float("inf"):
+            raise ValueError("sigma must be finite and > 0")
+        if shaping not in ES_SHAPINGS:
+            raise ValueError(f"shaping must be one of {ES_SHAPINGS}")
+        if self.noise == "reference":
+            raise ValueError("the gradient search draws from Philox: the reference has no draw order for it")
+        adam_coeffs(lr, betas, eps, 1)  # (refuses a bad lr / betas / eps before any work)
+        n, sigma = 2 * n_pairs, float(sigma)
+        g0, nl = self.shard(n)
+        shape = tuple(initial_noise.shape)
+        self._begin_search()
+        self.reserve(n, shape)
+        per = int(torch.Size(shape).numel())
+        lab = None if labels is None else labels.to(self.device).flatten().repeat(nl)
+        theta = initial_noise.to(self.device, torch.float32).contiguous().clone()
+        m, v = torch.zeros_like(theta), torch.zeros_like(theta)
+        w = torch.empty(n_pairs, dtype=torch.float32, device=self.device)
+        ws = self.es_workspace(n_pairs, per)
+        gn2 = torch.zeros(max(0, int(n_iterations)), dtype=torch.float64, device=self.device)
+        rms = torch.zeros_like(gn2)
+        best_noise, best_score = theta.clone(), float("-inf")
+        hist = {"scores": [], "grad_norms": [], "best_index": [], "candidates_per_iter": [], "pivot_rms": []}
+        for it in range(int(n_iterations)):
+            rid = 1 + it
+            x = self.es_candidates(rid, g0, nl, shape, theta, sigma)
+            self._denoise(rid, x, g0, per, lab)
+            r = self._finish_round(x, n, nl, g0, lab)
+            hist["scores"].append(r.scores.tolist())
+            hist["candidates_per_iter"].append(n)
+            hist["best_index"].append(r.best_index)
+            if r.best_score > best_score:
+                best_score = r.best_score
+                best_noise = self.es_candidates(rid, r.best_index, 1, shape, theta, sigma)  # (before theta moves)
+                self._keep_best_image(r, shape)
+            w.copy_(es_weights(r.scores, sigma, shaping))
+            self.es_update(rid, theta, m, v, w, adam_coeffs(lr, betas, eps, it + 1), ws, gn2[it:it + 1])
+            rms[it] = theta.double().square().mean().sqrt()
+        self._publish_best_image(shape)
+        hist["grad_norms"] = gn2.sqrt().tolist()  # (read once, after the last step)
+        hist["pivot_rms"] = rms.tolist()
+        return best_noise, best_score, self._hist(hist)
 
     # --- path search that branches at the injection steps
     def window_key(self, i: int, renoise_steps: int = 0) -> int:
@@ -588,6 +702,83 @@ class PathSearch:
             history["injection_points"].append(self.injection_step)
             if s > best_score:
                 best_score, best_noise = s, pert.clone()
+        return best_noise, best_score, history
+
+    def reset_nfes(self):
+        self.nfes = 0
+
+
+class GradientBasedSearch:
+    """``search_algorithm.py:343-438`` without autograd. The reference back-propagates ``-score`` through the sampler
+    (and fails on its ``no_grad`` sampler); here the gradient is the antithetic evolution-strategies estimate
+
+        g = 1 / (2 M sigma) * sum_p (s(theta + sigma z_p) - s(theta - sigma z_p)) z_p,   M = n_pairs,
+
+    which needs scores only, so every verifier works, and the reference's optimiser (Adam, ``lr``) steps on
+    grad = -g. ``shaping="rank"`` feeds centred ranks instead of raw scores (``es_weights``).
+
+    One difference: the reference tracks the best ITERATE; the iterate itself is never denoised here, so the best
+    EVALUATED candidate is tracked -- ``best_noise`` is the x_T of the best-scoring theta +- sigma z_p seen.
+    ``history`` keeps the reference's keys: ``scores`` (here one list of 2M scores an iteration) and ``grad_norms``."""
+
+    def __init__(self, n_iterations: int = 20, lr: float = 0.01, verbose: bool = False, *, n_pairs: int = 4,
+                 sigma: float = 0.05, shaping: str = "raw", betas: Tuple[float, float] = (0.9, 0.999),
+                 eps: float = 1e-8):
+        if shaping not in ES_SHAPINGS:
+            raise ValueError(f"shaping must be one of {ES_SHAPINGS}")
+        if int(n_pairs) < 1:
+            raise ValueError("n_pairs must be >= 1")
+        if not sigma > 0:
+            raise ValueError("sigma must be > 0")
+        self.n_iterations = n_iterations
+        self.lr = lr
+        self.verbose = verbose
+        self.n_pairs = int(n_pairs)
+        self.sigma = float(sigma)
+        self.shaping = shaping
+        self.betas = (float(betas[0]), float(betas[1]))
+        self.eps = float(eps)
+        self.nfes = 0
+
+    def search(self, initial_noise: torch.Tensor, denoise_fn: Callable, verifier_fn: Callable, device: str = "cuda",
+               batched: bool = False, sampler=None, seed: int = 0, **kwargs):
+        if batched:
+            eng = _engine(sampler, verifier_fn, seed, False)
+            out = eng.gradient_search(initial_noise, self.n_pairs, self.sigma, self.n_iterations, lr=self.lr,
+                                      betas=self.betas, eps=self.eps, shaping=self.shaping)
+            self.nfes += 2 * self.n_pairs * self.n_iterations
+            return out
+        theta = initial_noise.detach().clone().requires_grad_(True)  # (a leaf for the optimiser; never differentiated)
+        opt = torch.optim.Adam([theta], lr=self.lr, betas=self.betas, eps=self.eps)
+        best_noise, best_score = theta.detach().clone(), float("-inf")
+        history = {"scores": [], "grad_norms": []}
+        for it in range(self.n_iterations):
+            if self.verbose:
+                print(f"Gradient-Based Search Iteration {it + 1}/{self.n_iterations}")
+            pivot = theta.detach()
+            zs = [torch.randn_like(pivot) for _ in range(self.n_pairs)]
+            scores = []
+            for p, z in enumerate(zs):
+                for sign in (1.0, -1.0):
+                    cand = pivot + (sign * self.sigma) * z
+                    with torch.no_grad():
+                        den = denoise_fn(cand, **kwargs)
+                        self.nfes += 1
+                        s = verifier_fn(den, **kwargs)
+                    s = s.item() if isinstance(s, torch.Tensor) else s
+                    scores.append(s)
+                    if s > best_score:
+                        best_score, best_noise = s, cand.clone()
+            w = es_weights(scores, self.sigma, self.shaping).to(theta.device)
+            g = torch.zeros_like(pivot)
+            for wp, z in zip(w.tolist(), zs):
+                g += wp * z
+            theta.grad = -g  # the optimiser descends: maximise the score
+            opt.step()
+            history["scores"].append(scores)
+            history["grad_norms"].append(g.norm().item())
+            if self.verbose:
+                print(f"  Best score: {max(scores):.4f}, Grad Norm: {history['grad_norms'][-1]:.4f}")
         return best_noise, best_score, history
 
     def reset_nfes(self):
