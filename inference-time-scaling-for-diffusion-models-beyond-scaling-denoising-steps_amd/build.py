@@ -35,18 +35,24 @@ def _needs(obj, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build(verbose: bool = False, force: bool = False) -> str:
-    os.makedirs(OBJ, exist_ok=True)
+def flags_for(src, defines=()):
+    """The compile flags of one .hip file (the diagnostic builds and tools/regs.py use the same)."""
+    return FLAGS + FILE_FLAGS.get(os.path.basename(src), []) + list(defines)
+
+
+def build(verbose: bool = False, force: bool = False, defines=(), obj_dir: str = OBJ, lib: str = LIB) -> str:
+    """defines / obj_dir / lib: a variant library (extra hipcc definitions, its own objects, its own output)."""
+    os.makedirs(obj_dir, exist_ok=True)
     # every file a .hip may include (headers and .inc fragments) is a dependency of every object
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))]
     headers.append(os.path.join(INCLUDE, "itsd.h"))
     jobs = []
     objs = []
     for src in sources():
-        obj = os.path.join(OBJ, os.path.basename(src)[:-4] + ".o")
+        obj = os.path.join(obj_dir, os.path.basename(src)[:-4] + ".o")
         objs.append(obj)
         if force or _needs(obj, [src] + headers):
-            jobs.append([HIPCC] + FLAGS + FILE_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj])
+            jobs.append([HIPCC] + flags_for(src, defines) + ["-c", src, "-o", obj])
 
     def run(cmd):
         if verbose:
@@ -58,10 +64,17 @@ def build(verbose: bool = False, force: bool = False) -> str:
 
     with cf.ThreadPoolExecutor(max_workers=min(8, max(1, len(jobs)))) as ex:
         list(ex.map(run, jobs))
-    if force or jobs or _needs(LIB, objs):
-        run([HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", LIB] + objs)
-    return LIB
+    if force or jobs or _needs(lib, objs):
+        run([HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", lib] + objs)
+    return lib
 
 
 if __name__ == "__main__":
-    print(build(verbose=True, force="--force" in sys.argv))
+    # python build.py [--force] [--obj-dir DIR] [--out LIB] [-DNAME[=VALUE] ...]
+    argv = sys.argv[1:]
+    opt = {"--obj-dir": OBJ, "--out": LIB}
+    for k in opt:
+        if k in argv:
+            opt[k] = os.path.abspath(argv[argv.index(k) + 1])
+    print(build(verbose=True, force="--force" in argv, defines=[a for a in argv if a.startswith("-D")],
+                obj_dir=opt["--obj-dir"], lib=opt["--out"]))

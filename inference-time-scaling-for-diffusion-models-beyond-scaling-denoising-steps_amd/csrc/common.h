@@ -114,6 +114,80 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// ----------------------------------------------------------------------------- register-epilogue pieces
+// The MFMA kernels that write bf16 straight from their 32x32 accumulators (conv3x3_gn_p4 / p5_kernel,
+// head_mfma_kernel, the AttnBlock's attn_out_tile) share these: lane (rl, hh) of a wave holds pixel rl and, per
+// register group g, couts 8 g + 4 hh + 0..3. Every consumer-GroupNorm statistic they write goes through the one
+// tree below, which is why their sums agree to the bit. The helpers take values and array references and hold no
+// state between calls.
+
+// the value of lane ^ W: DPP within a row (W = 1, 2, 8), ds_swizzle otherwise
+template <int W> __device__ __forceinline__ float lane_xchg(float x) {
+  const int xi = __builtin_bit_cast(int, x);
+  int r;
+  if constexpr (W == 1) r = __builtin_amdgcn_update_dpp(0, xi, 0xB1, 0xF, 0xF, false);
+  else if constexpr (W == 2) r = __builtin_amdgcn_update_dpp(0, xi, 0x4E, 0xF, 0xF, false);
+  else if constexpr (W == 8) r = __builtin_amdgcn_update_dpp(0, xi, 0x128, 0xF, 0xF, false);
+  else r = __builtin_amdgcn_ds_swizzle(xi, 0x1F | (W << 10));
+  return __builtin_bit_cast(float, r);
+}
+// One halving step over v[0..N): lanes with bit D of rl keep the upper N / 2 values, the others the lower, each
+// summed with the partner lane's (rl ^ D) -> v[0..N / 2)
+template <int D, int N> __device__ __forceinline__ void stat_halve(float (&v)[32], int rl) {
+  const bool up = (rl & D) != 0;
+#pragma unroll
+  for (int i = 0; i < N / 2; ++i) {
+    const float lo = v[i], hi = v[i + N / 2];
+    v[i] = (up ? hi : lo) + lane_xchg<D>(up ? lo : hi);
+  }
+}
+// 32 values a lane (16 sums, 16 sums of squares) over the 32 lanes of a pixel block -> one a lane: lane rl ends
+// with v[0] = value index rl (rl < 16: the sum of cout 8 (e >> 2) + 4 hh + (e & 3), e = rl & 15; else its square sum)
+__device__ __forceinline__ void stat_butterfly32(float (&v)[32], int rl) {
+  stat_halve<16, 32>(v, rl);
+  stat_halve<8, 16>(v, rl);
+  stat_halve<4, 8>(v, rl);
+  stat_halve<2, 4>(v, rl);
+  stat_halve<1, 2>(v, rl);
+}
+__device__ __forceinline__ void stat_gather(float (&v)[32], const float (&s16)[16], const float (&q16)[16]) {
+#pragma unroll
+  for (int e = 0; e < 16; ++e) {
+    v[e] = s16[e];
+    v[16 + e] = q16[e];
+  }
+}
+// Register group g of one pixel block: acc + addv (+ the residual's four bf16, RES), rounded to bf16 once ->
+// wv[g][0..1]; the rounded values (0 for a pixel that is not live) join the sums s16 / square sums q16
+template <bool RES = true>
+__device__ __forceinline__ void epi_frag(int g, float a0, float a1, float a2, float a3, f32x4 ad, uint2 rr, bool live,
+                                         uint32_t (&wv)[4][2], float (&s16)[16], float (&q16)[16]) {
+  const float v0 = RES ? a0 + ad[0] + __uint_as_float(rr.x << 16) : a0 + ad[0];
+  const float v1 = RES ? a1 + ad[1] + __uint_as_float(rr.x & 0xffff0000u) : a1 + ad[1];
+  const float v2 = RES ? a2 + ad[2] + __uint_as_float(rr.y << 16) : a2 + ad[2];
+  const float v3 = RES ? a3 + ad[3] + __uint_as_float(rr.y & 0xffff0000u) : a3 + ad[3];
+  const bf16_t b0 = f2bf(v0), b1 = f2bf(v1), b2 = f2bf(v2), b3 = f2bf(v3);
+  wv[g][0] = (uint32_t)b0 | ((uint32_t)b1 << 16);
+  wv[g][1] = (uint32_t)b2 | ((uint32_t)b3 << 16);
+  const float m = live ? 1.0f : 0.0f;
+  const float r0 = bf2f(b0) * m, r1 = bf2f(b1) * m, r2 = bf2f(b2) * m, r3 = bf2f(b3) * m;
+  s16[4 * g + 0] += r0; q16[4 * g + 0] = fmaf(r0, r0, q16[4 * g + 0]);
+  s16[4 * g + 1] += r1; q16[4 * g + 1] = fmaf(r1, r1, q16[4 * g + 1]);
+  s16[4 * g + 2] += r2; q16[4 * g + 2] = fmaf(r2, r2, q16[4 * g + 2]);
+  s16[4 * g + 3] += r3; q16[4 * g + 3] = fmaf(r3, r3, q16[4 * g + 3]);
+}
+// Register groups gp, gp + 1 (gp = 0, 2) of both half-waves -> this lane's 16 B: couts 8 (gp + hh) + 0..7 of its pixel
+__device__ __forceinline__ u32x4 epi_pack(const uint32_t (&wv)[4][2], int gp) {
+  u32x4 o;
+#pragma unroll
+  for (int d = 0; d < 2; ++d) {
+    const auto sw = __builtin_amdgcn_permlane32_swap(wv[gp][d], wv[gp + 1][d], false, false);
+    o[d] = sw[0];
+    o[2 + d] = sw[1];
+  }
+  return o;
+}
+
 // ----------------------------------------------------------------------------- args
 // Implicit-GEMM convolution over NHWC activations (see conv.hip).
 struct ConvArgs {

@@ -164,6 +164,18 @@ __device__ __forceinline__ void addv_batch(const ConvArgs& a, int tileC, int img
 __device__ __forceinline__ long long temb_row_of(const ConvArgs& a) {
   return a.temb ? (a.temb_tsel ? (long long)(*a.temb_tsel) * a.temb_row_stride : 0) : 0;
 }
+// One additive value: bias + temb row + CFG cond row of (image img, cout co) (addv_batch above is the same sum with
+// the loads of a batch of entries issued together).
+__device__ __forceinline__ float addv_of(const ConvArgs& a, long long trow, int img, int co) {
+  float v = a.bias[co];
+  if (a.temb) v += a.temb[trow + (long long)img * a.temb_img_stride + co];
+  if (a.cemb) {
+    int lab = 0;
+    if (a.cemb_uncond_from < 0 || img < a.cemb_uncond_from) lab = a.cemb_labels[img % a.cemb_label_mod];
+    v += a.cemb[(long long)lab * a.cemb_row_stride + co];
+  }
+  return v;
+}
 
 // ADDV: floats of LDS after the fp32 tile for the staged additive rows (EPI_BYTES: 16 images of 128
 // couts); a tile holding more images (the 2x2 / 1x1 levels: 32 / 128 images per 128-pixel tile)
@@ -1524,61 +1536,40 @@ __device__ __forceinline__ void gn_silu_x4(uint32_t xa, uint32_t xb, float a0, f
         "s"(GN_L2E));
 }
 
-// ---------------------------------------------------------------------------- persistent, warp-specialized
-// conv3x3_gn_ws_kernel's stamps (profiles/r02_ws_stamps.txt): the MFMA waves keep the matrix pipe
-// ~88 % busy while they compute, but per 64-channel chunk they then wait ~5k cycles for the halo
-// waves (staging 14.5k cycles vs 10.5k of MFMA work: its 11 loads per lane are issued only when
-// the chunk starts), every tile begins with a ~10k-cycle exposed first-chunk staging, and ends with
-// a ~7k-cycle epilogue through a 128 KiB fp32 LDS tile. This kernel removes all three:
+// ---------------------------------------------------------------------------- persistent, one MFMA wave per SIMD
+// The fused GroupNorm+SiLU conv3x3 as one persistent, warp-specialized launch. A 512-thread block
+// runs 4 MFMA waves (one per SIMD, 64 couts x 128 pixels each: 8 MFMAs per k-step, 128
+// accumulators in AGPRs) beside 4 halo waves: 2 waves per SIMD, 256 registers each.
 //   * persistent: one block per CU walks the tiles t = blockIdx.x + k * gridDim.x; the 64-channel
 //     chunks of all its tiles form one stage sequence, double-buffered in LDS by stage parity;
-//   * halo waves (8..11) software-pipeline the stages as conv3x3_gn_ws_kernel's do: while
-//     transforming stage p they reload each item's register with stage p+1's item right after its
-//     transform, so HBM latency hides behind a whole chunk; during a tile's last chunk they stage
-//     the NEXT tile's first chunk and LDS-DMA this tile's residual rows into LDS (16-B units
-//     XOR-swizzled by row: conflict-free 8-B reads in the accumulator layout), and with its first
-//     chunk write its bias/temb rows;
-//   * MFMA waves (0..7) run the epilogue straight from their accumulators: + addv + residual,
-//     one rounding, 8-B stores, and the consumer GroupNorm statistics by a butterfly over the 32
-//     pixel lanes -- each wave's 128 pixels are whole statistics slots and its 32 couts are its
-//     own, so the statistics go straight to the slab: no LDS tile, no block barrier. Meanwhile
-//     the halo waves already stage the next tile's second chunk.
+//   * the halo waves software-pipeline the stages: while transforming stage p they reload each
+//     item's register with stage p+1's item right after its transform, so HBM latency hides
+//     behind a whole chunk; during a tile's last chunk they stage the NEXT tile's first chunk and
+//     LDS-DMA this tile's residual rows into LDS (16-B units XOR-swizzled by row: conflict-free
+//     8-B reads in the accumulator layout), and with its first chunk write its bias/temb rows;
+//   * the MFMA waves run the epilogue straight from their accumulators where the tile's
+//     statistics slots are a wave's own (the register-epilogue forms): + addv + residual, one
+//     rounding, 16-B stores, and the consumer GroupNorm statistics by a butterfly over the 32
+//     pixel lanes, straight to the slab: no LDS tile, no block barrier. Meanwhile the halo waves
+//     already stage the next tile's second chunk.
 // A fragments are prefetched across chunk and tile boundaries (the 6-slot ring never drains).
-// Per output the MFMA sequence is conv3x3_gn_reg_kernel's.
+// Why this shape (measurement records of the two-MFMA-waves-per-SIMD predecessors,
+// profiles/r02_ws_stamps.txt, profiles/r02_pws_ablations.txt): per 64-channel chunk the MFMA waves
+// waited ~5k cycles for halo waves that issued their loads only when the chunk started (staging
+// 14.5k cycles vs 10.5k of MFMA work), every tile began with a ~10k-cycle exposed first-chunk
+// staging and ended with a ~7k-cycle epilogue through a 128 KiB fp32 LDS tile; and with two MFMA
+// waves per SIMD each reading all 128 pixels' fragments of every k-step (1 KiB of LDS per MFMA)
+// inside a 168-register budget, a launch took 21 % less time without the B-fragment LDS reads
+// and 16 % less without the A-fragment loads.
 template <int W> struct GnpCfg;
 template <> struct GnpCfg<32> { static constexpr int NSEG = 1, ITEMS = 11, RES = 1; };
 template <> struct GnpCfg<16> { static constexpr int NSEG = 1, ITEMS = 11, RES = 1; };
 template <> struct GnpCfg<8> { static constexpr int NSEG = 4, ITEMS = 13, RES = 0; };  // LDS: residual from HBM
 
-
-// ---------------------------------------------------------------------------- persistent, one MFMA wave per SIMD
-// conv3x3_gn_pws_kernel's ablations (profiles/r02_pws_ablations.txt): without the B-fragment LDS
-// reads a launch takes 21 % less time, without the A-fragment loads 16 % less -- the two MFMA
-// waves per SIMD each read all 128 pixels' fragments of every k-step (1 KiB of LDS per MFMA)
-// and hide load latency only one k-step (B) / five k-steps (A) ahead inside a 168-register
-// budget. Here a 512-thread block runs 4 MFMA waves (one per SIMD, 64 couts x 128 pixels each:
-// 8 MFMAs per k-step, half the B reads per MFMA, 128 accumulators in AGPRs) beside the same 4
-// halo waves: 2 waves per SIMD, 256 registers each.
-#ifndef ITSD_P4_M16
-#define ITSD_P4_M16 2
-#endif
-#ifndef ITSD_P4_ZR8
-#define ITSD_P4_ZR8 1  // COMPACT 16x16x32 forms: 8 zero rows (a padding lane keeps its bank slot; 0: one, A/B builds)
-#endif
-#ifndef ITSD_P5_SC_LAUNCH
-#define ITSD_P5_SC_LAUNCH 7.5  // the standalone 1x1 launch a folded shortcut saves, in p5 chunk-times: round 5's 5 (3:
-                               // r05aq A/B) + the 2.4 by which round 6 re-priced a 2-slice combine (0.6 -> 3.0), so
-                               // that the folds round 5 measured faster stay chosen
-#endif
-#ifndef ITSD_P5_SWZ
-#define ITSD_P5_SWZ 1  // conv3x3_gn_p5_kernel's per-level halo swizzle at W <= 16 (0: (h >> 1) & 7; A/B builds)
-#endif
-#ifndef ITSD_P4_SUBSWZ
-#define ITSD_P4_SUBSWZ 1  // p4's non-compact 8x8 / 16x16 halo (sub-pixel forms) swizzled by halo coordinates (0: (h >> 1) & 7)
-#endif
-#ifndef ITSD_P4_HSWZ
-#define ITSD_P4_HSWZ 1  // the 16x16x32 forms' halo swizzle h & 6 (0: (h >> 1) & 7, as the 32x32x16 forms; A/B builds)
-#endif
+// cost-model constants of the p5 plan (chunk-times)
+constexpr double P5_SC_LAUNCH = 7.5;  // the standalone 1x1 launch a folded shortcut saves, in p5 chunk-times: round 5's 5 (3:
+                                      // r05aq A/B) + the 2.4 by which round 6 re-priced a 2-slice combine (0.6 -> 3.0), so
+                                      // that the folds round 5 measured faster stay chosen
 constexpr int P4_RING = 6;  // A k-step slots (prefetch distance 5 k-steps = 40 MFMAs); divides the 36 k-steps
                             // of a chunk, so the slots of the next chunk's prefetched steps line up
 constexpr int P4_BD = 2;    // B fragment buffers (reads P4_BD - 1 k-steps = 8 MFMAs ahead)
@@ -1610,12 +1601,12 @@ __global__ __launch_bounds__(512, 1) void conv3x3_gn_p4_kernel(ConvArgs a) {
   constexpr int TPS = 256 / NSEG, RPP = TPS / 8;
   constexpr int ZROW = GNW_BN;  // COMPACT: the zero row
   // M16: the MFMA waves on v_mfma_f32_16x16x32_bf16 (the LDS residual / output tile forms; the sub-pixel and
-  // register-epilogue forms stay on 32x32x16). ITSD_P4_M16: 0 none, 1 the 32x32 level, 2 every RES form
-  constexpr bool M16 = ITSD_P4_M16 >= 1 && RES && !SUB && (AB & 1) == 0 && (W == 32 || ITSD_P4_M16 >= 2);
+  // register-epilogue forms stay on 32x32x16)
+  constexpr bool M16 = RES && !SUB && (AB & 1) == 0;
   // (COMPACT + M16: 8 zero rows, a lane whose tap falls outside its image reads the one with its own row's residue
   // mod 8 -- its own bank slot under hswz, so the zero reads do not collide with the group's real rows -- and 8 more
   // 64 rows past them, read at the +64-row immediate offset of pixel blocks 4..7)
-  constexpr int ZROWS = COMPACT ? (M16 ? (ITSD_P4_ZR8 ? 72 : 65) : 1) : 0;
+  constexpr int ZROWS = COMPACT ? (M16 ? 72 : 1) : 0;
   // halo row h's 16-B units are stored XOR-permuted by hswz(h). ds_read_b128 serves a wave in four 16-lane groups
   // ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, +32: MI355X_MICROARCH.md, LDS) over 16 slots of 16 B (row parity x
   // unit). The 32x32x16 B reads (lane = 32 rows x 2 halves) are conflict-free for any tap offset with
@@ -1623,12 +1614,12 @@ __global__ __launch_bounds__(512, 1) void conv3x3_gn_p4_kernel(ConvArgs a) {
   // and +4-11 of the other) were 2-way at 3 of every 4 row offsets with it (the round-5 7x rise of
   // SQ_LDS_BANK_CONFLICT, profiles/r05/p4_lds_conflicts_r05ab.txt), and are conflict-free at every offset with
   // h & 6 (exhaustive check over offsets, groups and both half-steps: tools/halo_swizzle.py)
-  auto hswz = [](int h) { return M16 && ITSD_P4_HSWZ ? (h & 6) : ((h >> 1) & 7); };
+  auto hswz = [](int h) { return M16 ? (h & 6) : ((h >> 1) & 7); };
   // The non-compact halo at 8x8 / 16x16 (the sub-pixel forms' input grids): a 32-pixel block spans image rows of
   // W + 2-row pitch, so (h >> 1) & 7 left 37 % / 12 % of the 32x32x16 B reads' lanes on a taken bank slot (9.4e6
   // conflict cycles a <8, 128> / <16, 128> launch at N = 256); halo coordinates instead: unit ^ (hy + SC2 hx) & 7
   // (as conv3x3_gn_p5_kernel's halo; tools/halo_swizzle.py --p5 geometry)
-  constexpr bool CSWZ = ITSD_P4_SUBSWZ && !COMPACT && !M16 && W <= 16;
+  constexpr bool CSWZ = !COMPACT && !M16 && W <= 16;
   constexpr int SC1 = 1, SC2 = W <= 8 ? 2 : 1;
   // C96 (AB bit 512, 8x8 only): 96-cout tiles -- Cout = 384 gives 4 cout tiles, so N = 256's 64 pixel tiles make
   // 256 tiles for the 256 CUs instead of 192 with 128 couts (a quarter of the chip idle). Each MFMA wave holds 48
@@ -1724,17 +1715,10 @@ __global__ __launch_bounds__(512, 1) void conv3x3_gn_p4_kernel(ConvArgs a) {
   // bias (+ time / class embedding) of tile k's couts (and image segments) -> addv[k & 1]
   auto stage_addv = [&](int k, int t0) {  // threads t0 .. t0+255
     const int tileP = tile_p(k), tileC = tile_c(k), img0 = tileP / (H * W);
-    const long long trow = a.temb ? (a.temb_tsel ? (long long)(*a.temb_tsel) * a.temb_row_stride : 0) : 0;
+    const long long trow = temb_row_of(a);
     for (int it = t0; it < NSEG * BM; it += 256) {
       const int il = it / BM, cl = it - il * BM, co = tileC + cl, img = img0 + il;
-      float v = a.bias[co];
-      if (a.temb) v += a.temb[trow + (long long)img * a.temb_img_stride + co];
-      if (a.cemb) {
-        int lab = 0;
-        if (a.cemb_uncond_from < 0 || img < a.cemb_uncond_from) lab = a.cemb_labels[img % a.cemb_label_mod];
-        v += a.cemb[(long long)lab * a.cemb_row_stride + co];
-      }
-      addv[(k & 1) * NSEG * BM + it] = v;
+      addv[(k & 1) * NSEG * BM + it] = addv_of(a, trow, img, co);
     }
   };
 
@@ -1861,7 +1845,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_gn_p4_kernel(ConvArgs a) {
                 const int x = (p0 & (W - 1)) + kx - 1, y = (((p0 / W) + t * (16 / W)) & (W - 1)) + ky - 1;
                 const bool ok = (unsigned)x < (unsigned)W && (W == 16 || (unsigned)y < (unsigned)W);
                 const int hw = p0 + 16 * t + (ky - 1) * W + (kx - 1);
-                h = ok ? hw : ZROW + (ITSD_P4_ZR8 && W == 8 ? (hw & 7) : 0);  // (16x16: one zero row; 8 rows by residue spilled)
+                h = ok ? hw : ZROW + (W == 8 ? (hw & 7) : 0);  // (16x16: one zero row; 8 rows by residue spilled)
               } else {
                 h = p0 + t * W2 + ky * W2 + kx;  // block 2t
               }
@@ -2224,63 +2208,18 @@ __global__ __launch_bounds__(512, 1) void conv3x3_gn_p4_kernel(ConvArgs a) {
                                 : (const T*)zero_of_block<T>(a);
           uint2 rr = *(const uint2*)rp;
           if (!has_res) rr = uint2{0u, 0u};  // select, not a branch
-          float v[4];
-          v[0] = acc[i][j][4 * g + 0] + ad[0] + __uint_as_float(rr.x << 16);
-          v[1] = acc[i][j][4 * g + 1] + ad[1] + __uint_as_float(rr.x & 0xffff0000u);
-          v[2] = acc[i][j][4 * g + 2] + ad[2] + __uint_as_float(rr.y << 16);
-          v[3] = acc[i][j][4 * g + 3] + ad[3] + __uint_as_float(rr.y & 0xffff0000u);
-          const T b0 = f2bf(v[0]), b1 = f2bf(v[1]), b2 = f2bf(v[2]), b3 = f2bf(v[3]);
-          wv[g][0] = (uint32_t)b0 | ((uint32_t)b1 << 16);
-          wv[g][1] = (uint32_t)b2 | ((uint32_t)b3 << 16);
-          const float r0 = bf2f(b0), r1 = bf2f(b1), r2 = bf2f(b2), r3 = bf2f(b3);
-          s16[4 * g + 0] += r0; q16[4 * g + 0] = fmaf(r0, r0, q16[4 * g + 0]);
-          s16[4 * g + 1] += r1; q16[4 * g + 1] = fmaf(r1, r1, q16[4 * g + 1]);
-          s16[4 * g + 2] += r2; q16[4 * g + 2] = fmaf(r2, r2, q16[4 * g + 2]);
-          s16[4 * g + 3] += r3; q16[4 * g + 3] = fmaf(r3, r3, q16[4 * g + 3]);
+          epi_frag(g, acc[i][j][4 * g + 0], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3], ad, rr,
+                   true, wv, s16, q16);
         }
 #pragma unroll
         for (int gp = 0; gp < 4; gp += 2) {
-          u32x4 o;
-#pragma unroll
-          for (int d = 0; d < 2; ++d) {
-            const auto sw = __builtin_amdgcn_permlane32_swap(wv[gp][d], wv[gp + 1][d], false, false);
-            o[d] = sw[0];
-            o[2 + d] = sw[1];
-          }
           const int c8 = wmi * 32 + 8 * (gp + hh);
-          *(u32x4*)((T*)a.out + orow(tileP + p, tph) * a.Cout + tileC + c8) = o;
+          *(u32x4*)((T*)a.out + orow(tileP + p, tph) * a.Cout + tileC + c8) = epi_pack(wv, gp);
         }
         if (a.stats && ((NSEG == 1 && j == 3) || (NSEG != 1 && (j & 1)))) {
           float v[32];
-#pragma unroll
-          for (int e = 0; e < 16; ++e) {
-            v[e] = s16[e];
-            v[16 + e] = q16[e];
-          }
-          auto xchg = [](float x, auto wc) {
-            constexpr int w = decltype(wc)::value;
-            const int xi = __builtin_bit_cast(int, x);
-            int r;
-            if constexpr (w == 1) r = __builtin_amdgcn_update_dpp(0, xi, 0xB1, 0xF, 0xF, false);
-            else if constexpr (w == 2) r = __builtin_amdgcn_update_dpp(0, xi, 0x4E, 0xF, 0xF, false);
-            else if constexpr (w == 8) r = __builtin_amdgcn_update_dpp(0, xi, 0x128, 0xF, 0xF, false);
-            else r = __builtin_amdgcn_ds_swizzle(xi, 0x1F | (w << 10));
-            return __builtin_bit_cast(float, r);
-          };
-          auto halve = [&](auto wc) {
-            constexpr int w = decltype(wc)::value;
-            const bool up = (rl & w) != 0;
-#pragma unroll
-            for (int ii = 0; ii < w; ++ii) {
-              const float lo = v[ii], hi = v[ii + w];
-              v[ii] = (up ? hi : lo) + xchg(up ? lo : hi, wc);
-            }
-          };
-          halve(std::integral_constant<int, 16>{});
-          halve(std::integral_constant<int, 8>{});
-          halve(std::integral_constant<int, 4>{});
-          halve(std::integral_constant<int, 2>{});
-          halve(std::integral_constant<int, 1>{});
+          stat_gather(v, s16, q16);
+          stat_butterfly32(v, rl);
           {
             constexpr int SLOT = NSEG == 1 ? 128 : 64;
             long long slot = (long long)(tileP + wn * 128 + (NSEG == 1 ? 0 : (j >> 1) * 64)) / SLOT;
@@ -2324,7 +2263,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_gn_p4_kernel(ConvArgs a) {
   }
 
   // ================================================================== halo waves
-  // (conv3x3_gn_ws_kernel's halo pipeline, over the block's whole stage sequence.) Item j of this
+  // (One software pipeline over the block's whole stage sequence.) Item j of this
   // thread = halo row (lt >> 3) + RPP * j of its image segment, 8 channels (lch). Per tile, for
   // the loads: the input pixel of each item (0 for padding / scratch rows: a valid address,
   // never used); for the LDS writes: each item's address (its halo row, or a dump row past the
@@ -2332,7 +2271,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_gn_p4_kernel(ConvArgs a) {
   // padding rows differ between tiles). Stage and tile indices advance by counters (no divides).
   const int tt = tid - 256, lch = tt & 7, sg = tt / TPS, lt = tt - sg * TPS;
   static_assert(COMPACT || NSEG * ITEMS * RPP > NSEG * HS, "a scratch row exists");
-  if (a.dbg & (1 << 20)) __builtin_amdgcn_s_setprio(1);  // measurement switches, as in the ws kernel
+  if (a.dbg & (1 << 20)) __builtin_amdgcn_s_setprio(1);  // measurement switches (the conv_dbg option)
   if (a.dbg & (1 << 21)) __builtin_amdgcn_s_setprio(2);
   const int dump = NSEG * HS * ROWB + (lch << 4);  // (not COMPACT: the scratch rows' write target)
   const int hrow0 = (COMPACT ? sg * HWs : sg * HS) + (lt >> 3), hrow1 = hrow0 + RPP;
@@ -2518,12 +2457,9 @@ __global__ __launch_bounds__(512, 1) void conv3x3_gn_p4_kernel(ConvArgs a) {
         if (a.stats) {
           auto xchg = [&](float x, auto wc) {
             constexpr int w = decltype(wc)::value;
-            const int xi = __builtin_bit_cast(int, x);
-            int r;
-            if constexpr (w == 8) r = __builtin_amdgcn_update_dpp(0, xi, 0x128, 0xF, 0xF, false);  // row_ror:8
-            else if constexpr (w == 16) r = __builtin_amdgcn_ds_swizzle(xi, 0x1F | (16 << 10));
-            else r = __builtin_amdgcn_ds_bpermute((lane ^ 32) << 2, xi);
-            return __builtin_bit_cast(float, r);
+            if constexpr (w < 32) return lane_xchg<w>(x);
+            else  // (the other half-wave: past ds_swizzle's 32 lanes)
+              return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((lane ^ 32) << 2, __builtin_bit_cast(int, x)));
           };
           auto halve = [&](auto wc, int n) {
             const bool up = (lane & decltype(wc)::value) != 0;
@@ -2648,7 +2584,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_gn_p4_kernel(ConvArgs a) {
   }
   if constexpr (COMPACT) {  // the zero row of both halo buffers (no stage writes it; read after B0)
     if (tt < 16) *(u32x4*)(smem + (tt >> 3) * HALO + ZROW * ROWB + ((tt & 7) << 4)) = u32x4{0u, 0u, 0u, 0u};
-    if (M16 && ITSD_P4_ZR8) {  // rows ZROW + 0..7 and + 64..71 of both buffers: one 16-B unit a thread
+    if (M16) {  // rows ZROW + 0..7 and + 64..71 of both buffers: one 16-B unit a thread
       const int r = (tt >> 3) & 15;
       *(u32x4*)(smem + (tt >> 7) * HALO + (ZROW + (r & 7) + (r >> 3) * 64) * ROWB + ((tt & 7) << 4)) = u32x4{0u, 0u, 0u, 0u};
     } else if (M16 && tt >= 16 && tt < 32) {
@@ -2735,15 +2671,9 @@ template <int W> struct Gp5Cfg {
   static constexpr int TPS = 256 / NSEG, RPP = TPS / 8, ITEMS = NHY * W / RPP;
   static constexpr int HALO = ((NSEG * HS * ROWB) + 1023) & ~1023;  // one halo buffer (bytes)
 };
-#ifndef ITSD_P5_RING
-#define ITSD_P5_RING 9
-#endif
-#ifndef ITSD_P5_BD
-#define ITSD_P5_BD 3
-#endif
-constexpr int P5_RING = ITSD_P5_RING;  // A k-step slots (prefetch distance 8 k-steps = 32 MFMAs); divides 36
+constexpr int P5_RING = 9;  // A k-step slots (prefetch distance 8 k-steps = 32 MFMAs); divides 36
                             // (12 and 18 measured equal at N = 32 and 256)
-constexpr int P5_BD = ITSD_P5_BD;    // B fragment buffers (reads two k-steps = 8 MFMAs ahead)
+constexpr int P5_BD = 3;  // B fragment buffers (reads two k-steps = 8 MFMAs ahead)
 // (round 5: the MFMA waves on v_mfma_f32_16x16x32_bf16 as in p4 -- 2 x 8 f32x4 accumulators, 6-slot k32 A ring, 8-B
 // stores, per-slot butterflies over the 16 pixel lanes -- measured N = 256 equal, N = 32 +2.3 %, N = 64 +0.7 %, C4
 // +0.7 % step time against this form, profiles/r05/step_p5_m16_vs_m32.txt: removed)
@@ -2771,7 +2701,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_gn_p5_kernel(ConvArgs a) {
   // launch's 4.8e6 conflict cycles (profiles/r05/pmc_dispatch_table_r05ae.txt). A slot is (hx & 1, swz) (W2 even);
   // these keep every group of every tap on 16 distinct slots (exhaustive check: tools/halo_swizzle.py --p5)
   constexpr int SC1 = 1, SC2 = W <= 8 ? 2 : 1;
-  auto swz = [](int hy, int hx, int h) { return W <= 16 && ITSD_P5_SWZ ? (SC1 * hy + SC2 * hx) & 7 : (h >> 1) & 7; };
+  auto swz = [](int hy, int hx, int h) { return W <= 16 ? (SC1 * hy + SC2 * hx) & 7 : (h >> 1) & 7; };
   static_assert(NSEG * SPX == 128 && ITEMS * RPP == NHY * W && ITEMS <= 31 && 36 % P5_RING == 0, "p5 geometry");
   constexpr int SEGW = 64 / TPS > 0 ? 64 / TPS : 1;  // image segments one halo wave covers (W = 4: 2)
   // + the residual tiles of two items [item parity][128 px][128 couts] bf16 (LDS-DMA'd by the halo waves
@@ -2837,7 +2767,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_gn_p5_kernel(ConvArgs a) {
     }
     // B unit of pixel block j at tap (ky, kx): halo row h = hb[j] + ky W2 + kx, hy = y + ky, hx = x + kx
     auto bunit = [&](int j, int h, int ky, int kx) {
-      return W <= 16 && ITSD_P5_SWZ ? (hq[j] + SC1 * ky + SC2 * kx) & 7 : (h >> 1) & 7;
+      return W <= 16 ? (hq[j] + SC1 * ky + SC2 * kx) & 7 : (h >> 1) & 7;
     };
     const uint32_t ablk = (uint32_t)(9 * kpt) * 1024;  // one 32-cout block of fragments
     // A fragments by buffer loads (conv3x3_gn_p4_kernel's scheme): voffset = this lane's 16 B of the wave's
@@ -3110,22 +3040,12 @@ __global__ __launch_bounds__(512, 1) void conv3x3_gn_p5_kernel(ConvArgs a) {
           const int tileP = tp * 128, tileC = tc * CONV_BM;
           const int nfrag = nown * NJ, F = 16 / ST;  // fragments (unit, jj) of this wave; a batch of F x ST slots
           f32x4 s4 = {0.f, 0.f, 0.f, 0.f}, q4 = {0.f, 0.f, 0.f, 0.f};
-          // lane exchange with lane ^ w (as the last-arriver epilogue's statistics: DPP within a row, else swizzle)
-          auto xchg = [](float x, auto wc) {
-            constexpr int w = decltype(wc)::value;
-            const int xi = __builtin_bit_cast(int, x);
-            int r;
-            if constexpr (w == 1) r = __builtin_amdgcn_update_dpp(0, xi, 0xB1, 0xF, 0xF, false);
-            else if constexpr (w == 2) r = __builtin_amdgcn_update_dpp(0, xi, 0x4E, 0xF, 0xF, false);
-            else if constexpr (w == 8) r = __builtin_amdgcn_update_dpp(0, xi, 0x128, 0xF, 0xF, false);
-            else r = __builtin_amdgcn_ds_swizzle(xi, 0x1F | (w << 10));
-            return __builtin_bit_cast(float, r);
-          };
           auto bfly = [&](auto wc) {
+            constexpr int w = decltype(wc)::value;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-              s4[e] += xchg(s4[e], wc);
-              q4[e] += xchg(q4[e], wc);
+              s4[e] += lane_xchg<w>(s4[e]);
+              q4[e] += lane_xchg<w>(q4[e]);
             }
           };
           for (int f0 = 0; f0 < nfrag; f0 += F) {
@@ -3319,30 +3239,11 @@ __global__ __launch_bounds__(512, 1) void conv3x3_gn_p5_kernel(ConvArgs a) {
           const f32x4 ad = *(const f32x4*)(avj + 8 * g);
           uint2 rr = *(const uint2*)(rk + pl * 256 + ((((c >> 3) ^ pl) & 15) << 4) + 8 * hh);
           if (!has_res) rr = uint2{0u, 0u};
-          float v[4];
-          v[0] = acc[j][4 * g + 0] + ad[0] + __uint_as_float(rr.x << 16);
-          v[1] = acc[j][4 * g + 1] + ad[1] + __uint_as_float(rr.x & 0xffff0000u);
-          v[2] = acc[j][4 * g + 2] + ad[2] + __uint_as_float(rr.y << 16);
-          v[3] = acc[j][4 * g + 3] + ad[3] + __uint_as_float(rr.y & 0xffff0000u);
-          const T b0 = f2bf(v[0]), b1 = f2bf(v[1]), b2 = f2bf(v[2]), b3 = f2bf(v[3]);
-          wv[g][0] = (uint32_t)b0 | ((uint32_t)b1 << 16);
-          wv[g][1] = (uint32_t)b2 | ((uint32_t)b3 << 16);
-          const float m = live ? 1.0f : 0.0f;
-          const float r0 = bf2f(b0) * m, r1 = bf2f(b1) * m, r2 = bf2f(b2) * m, r3 = bf2f(b3) * m;
-          s16[4 * g + 0] += r0; q16[4 * g + 0] = fmaf(r0, r0, q16[4 * g + 0]);
-          s16[4 * g + 1] += r1; q16[4 * g + 1] = fmaf(r1, r1, q16[4 * g + 1]);
-          s16[4 * g + 2] += r2; q16[4 * g + 2] = fmaf(r2, r2, q16[4 * g + 2]);
-          s16[4 * g + 3] += r3; q16[4 * g + 3] = fmaf(r3, r3, q16[4 * g + 3]);
+          epi_frag(g, acc[j][4 * g + 0], acc[j][4 * g + 1], acc[j][4 * g + 2], acc[j][4 * g + 3], ad, rr, live, wv, s16, q16);
         }
 #pragma unroll
         for (int gp = 0; gp < 4; gp += 2) {
-          u32x4 o;
-#pragma unroll
-          for (int d = 0; d < 2; ++d) {
-            const auto sw = __builtin_amdgcn_permlane32_swap(wv[gp][d], wv[gp + 1][d], false, false);
-            o[d] = sw[0];
-            o[2 + d] = sw[1];
-          }
+          const u32x4 o = epi_pack(wv, gp);
           const int c8 = cw * 32 + 8 * (gp + hh);
           if (live) *(u32x4*)((T*)a.out + (size_t)(tileP + pl) * a.Cout + tileC + c8) = o;
         }
@@ -3350,45 +3251,17 @@ __global__ __launch_bounds__(512, 1) void conv3x3_gn_p5_kernel(ConvArgs a) {
         // W = 4: lanes 0-15 / 16-31 of each j-block), one per 128-pixel tile (W >= 16: all four)
         if (a.stats && (W == 4 || (W == 8 && (j & 1)) || j == 3)) {
           float v[32];
-#pragma unroll
-          for (int e = 0; e < 16; ++e) {
-            v[e] = s16[e];
-            v[16 + e] = q16[e];
-          }
-          auto xchg = [](float x, auto wc) {
-            constexpr int w = decltype(wc)::value;
-            const int xi = __builtin_bit_cast(int, x);
-            int r;
-            if constexpr (w == 1) r = __builtin_amdgcn_update_dpp(0, xi, 0xB1, 0xF, 0xF, false);
-            else if constexpr (w == 2) r = __builtin_amdgcn_update_dpp(0, xi, 0x4E, 0xF, 0xF, false);
-            else if constexpr (w == 8) r = __builtin_amdgcn_update_dpp(0, xi, 0x128, 0xF, 0xF, false);
-            else r = __builtin_amdgcn_ds_swizzle(xi, 0x1F | (w << 10));
-            return __builtin_bit_cast(float, r);
-          };
-          // halve(d, n): lanes with bit d of rl keep the upper n/2 values, each summed with its partner's
-          auto halve = [&](auto wc, auto nc) {
-            constexpr int d = decltype(wc)::value, n = decltype(nc)::value;
-            const bool up = (rl & d) != 0;
-#pragma unroll
-            for (int ii = 0; ii < n / 2; ++ii) {
-              const float lo = v[ii], hi = v[ii + n / 2];
-              v[ii] = (up ? hi : lo) + xchg(up ? lo : hi, wc);
-            }
-          };
+          stat_gather(v, s16, q16);
           if constexpr (W >= 8) {  // 64-pixel slot (W = 8: 2 j-blocks) / 128-pixel slot: one value a lane
-            halve(std::integral_constant<int, 16>{}, std::integral_constant<int, 32>{});
-            halve(std::integral_constant<int, 8>{}, std::integral_constant<int, 16>{});
-            halve(std::integral_constant<int, 4>{}, std::integral_constant<int, 8>{});
-            halve(std::integral_constant<int, 2>{}, std::integral_constant<int, 4>{});
-            halve(std::integral_constant<int, 1>{}, std::integral_constant<int, 2>{});
+            stat_butterfly32(v, rl);
             const long long slot = W == 8 ? tp * NSEG + ((jb0 + j) >> 1) : tp;  // = global pixel / stat_slot_px
             const int e = rl & 15, co = cw * 32 + 8 * (e >> 2) + 4 * hh + (e & 3);
             if (slot * (W == 8 ? 64 : 128) < a.M) a.stats[(slot * 2 + (rl >> 4)) * a.Cout + tileC + co] = v[0];
           } else {  // 16-pixel slot = 16 lanes: two values a lane, idx = 2 (rl & 15) + {0, 1}
-            halve(std::integral_constant<int, 8>{}, std::integral_constant<int, 32>{});
-            halve(std::integral_constant<int, 4>{}, std::integral_constant<int, 16>{});
-            halve(std::integral_constant<int, 2>{}, std::integral_constant<int, 8>{});
-            halve(std::integral_constant<int, 1>{}, std::integral_constant<int, 4>{});
+            stat_halve<8, 32>(v, rl);
+            stat_halve<4, 16>(v, rl);
+            stat_halve<2, 8>(v, rl);
+            stat_halve<1, 4>(v, rl);
             const int img = tp * NSEG + 2 * (jb0 + j) + (rl >> 4);
             const int m = rl & 7, co = cw * 32 + 8 * (m >> 1) + 4 * hh + 2 * (m & 1);
             if (img < nimg) *(float2*)(a.stats + ((long long)img * 2 + ((rl >> 3) & 1)) * a.Cout + tileC + co) = float2{v[0], v[1]};
@@ -3625,18 +3498,11 @@ __global__ __launch_bounds__(512, 1) void conv3x3_gn_p5_kernel(ConvArgs a) {
   auto stage_addv = [&](int k) {  // bias (+ time / class embedding) of item k's images x couts
     int tp, tc, z;
     item_of(k, tp, tc, z);
-    const long long trow = a.temb ? (a.temb_tsel ? (long long)(*a.temb_tsel) * a.temb_row_stride : 0) : 0;
+    const long long trow = temb_row_of(a);
     for (int it = tt; it < NSEG * CB; it += 256) {  // [image of the tile][CB couts]
       const int il = it / CB, cl = it % CB, co = tc * CB + cl;
       const int img = min(Cf::ROWS ? (tp * 128) / HW : tp * NSEG + il, nimg - 1);
-      float v = a.bias[co];
-      if (a.temb) v += a.temb[trow + (long long)img * a.temb_img_stride + co];
-      if (a.cemb) {
-        int lab = 0;
-        if (a.cemb_uncond_from < 0 || img < a.cemb_uncond_from) lab = a.cemb_labels[img % a.cemb_label_mod];
-        v += a.cemb[(long long)lab * a.cemb_row_stride + co];
-      }
-      addv[(k & 1) * NSEG * CONV_BM + it] = v;
+      addv[(k & 1) * NSEG * CONV_BM + it] = addv_of(a, trow, img, co);
     }
   };
   // prologue: stage 0 into buffer 0 (stage 1 loading)
@@ -3856,60 +3722,19 @@ __global__ __launch_bounds__(256, 4) void head_mfma_kernel(HeadArgs h) {
     for (int g = 0; g < 4; ++g) {
       const int c = tileC + wid * 32 + 8 * g + 4 * hh;
       const f32x4 bb = *(const f32x4*)(h.b + c);
-      const T b0 = f2bf(acc[j][4 * g] + bb[0]), b1 = f2bf(acc[j][4 * g + 1] + bb[1]);
-      const T b2 = f2bf(acc[j][4 * g + 2] + bb[2]), b3 = f2bf(acc[j][4 * g + 3] + bb[3]);
-      wv[g][0] = (uint32_t)b0 | ((uint32_t)b1 << 16);
-      wv[g][1] = (uint32_t)b2 | ((uint32_t)b3 << 16);
-      const float r0 = bf2f(b0), r1 = bf2f(b1), r2 = bf2f(b2), r3 = bf2f(b3);
-      s16[4 * g + 0] += r0; q16[4 * g + 0] = fmaf(r0, r0, q16[4 * g + 0]);
-      s16[4 * g + 1] += r1; q16[4 * g + 1] = fmaf(r1, r1, q16[4 * g + 1]);
-      s16[4 * g + 2] += r2; q16[4 * g + 2] = fmaf(r2, r2, q16[4 * g + 2]);
-      s16[4 * g + 3] += r3; q16[4 * g + 3] = fmaf(r3, r3, q16[4 * g + 3]);
+      epi_frag<false>(g, acc[j][4 * g + 0], acc[j][4 * g + 1], acc[j][4 * g + 2], acc[j][4 * g + 3], bb, uint2{0u, 0u},
+                      true, wv, s16, q16);
     }
 #pragma unroll
     for (int gp = 0; gp < 4; gp += 2) {
-      u32x4 o;
-#pragma unroll
-      for (int d = 0; d < 2; ++d) {
-        const auto sw = __builtin_amdgcn_permlane32_swap(wv[gp][d], wv[gp + 1][d], false, false);
-        o[d] = sw[0];
-        o[2 + d] = sw[1];
-      }
       const int c8 = tileC + wid * 32 + 8 * (gp + hh);
-      if (live) *(u32x4*)((T*)h.out + (size_t)(tileP + pl) * h.Cout + c8) = o;
+      if (live) *(u32x4*)((T*)h.out + (size_t)(tileP + pl) * h.Cout + c8) = epi_pack(wv, gp);
     }
   }
-  if (h.stats && live) {  // the tile's 128 pixels = one slot: 32 values a lane -> one (p5's W >= 16 butterfly)
+  if (h.stats && live) {  // the tile's 128 pixels = one slot: 32 values a lane -> one
     float v[32];
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      v[e] = s16[e];
-      v[16 + e] = q16[e];
-    }
-    auto xchg = [](float x, auto wc) {
-      constexpr int w = decltype(wc)::value;
-      const int xi = __builtin_bit_cast(int, x);
-      int r;
-      if constexpr (w == 1) r = __builtin_amdgcn_update_dpp(0, xi, 0xB1, 0xF, 0xF, false);
-      else if constexpr (w == 2) r = __builtin_amdgcn_update_dpp(0, xi, 0x4E, 0xF, 0xF, false);
-      else if constexpr (w == 8) r = __builtin_amdgcn_update_dpp(0, xi, 0x128, 0xF, 0xF, false);
-      else r = __builtin_amdgcn_ds_swizzle(xi, 0x1F | (w << 10));
-      return __builtin_bit_cast(float, r);
-    };
-    auto halve = [&](auto wc) {
-      constexpr int d = decltype(wc)::value;
-      const bool up = (rl & d) != 0;
-#pragma unroll
-      for (int ii = 0; ii < d; ++ii) {
-        const float lo = v[ii], hi = v[ii + d];
-        v[ii] = (up ? hi : lo) + xchg(up ? lo : hi, wc);
-      }
-    };
-    halve(std::integral_constant<int, 16>{});
-    halve(std::integral_constant<int, 8>{});
-    halve(std::integral_constant<int, 4>{});
-    halve(std::integral_constant<int, 2>{});
-    halve(std::integral_constant<int, 1>{});
+    stat_gather(v, s16, q16);
+    stat_butterfly32(v, rl);
     const long long slot = tileP / 128;
     const int e = rl & 15, co = wid * 32 + 8 * (e >> 2) + 4 * hh + (e & 3);
     h.stats[(slot * 2 + (rl >> 4)) * h.Cout + tileC + co] = v[0];
@@ -3974,10 +3799,8 @@ static double p5_combine_cost(int tiles, int st, int cb, int W) {
   if (st <= 1) return 0.0;
   return cb == 128 && p5_dist(tiles, st, W) ? 2.5 : 2.0 + 0.5 * st;
 }
-// 64-cout items (CB = 64, W <= 8): a chunk's MFMA work halves, its staging does not -- ITSD_P5_C64_CHUNK chunk-times
-#ifndef ITSD_P5_C64_CHUNK
-#define ITSD_P5_C64_CHUNK 0.6
-#endif
+// 64-cout items (CB = 64, W <= 8): a chunk's MFMA work halves, its staging does not -- P5_C64_CHUNK chunk-times
+constexpr double P5_C64_CHUNK = 0.6;
 
 // K slices of a p5 launch at cout tile cb: the S minimising ceil(items / CUs) x (chunks per slice x chunk cost + ~1.5
 // chunks of prologue / epilogue) + the combine, bounded by the slab and ticket capacities
@@ -4001,7 +3824,7 @@ static int p5_split(const ConvArgs& a, int tiles, int nch, int cb, double fc) {
 // 96-cout tiles of conv3x3_gn_p4_kernel<8> (AB 512)? Where the 128-cout tile count leaves CUs idle and 96-cout
 // tiles need fewer tile-rounds x tile cost (ceil(NT / CUs) x BM / 128), e.g. N = 256: 192 -> 256 tiles
 static bool p4_c96(const ConvArgs& a) {
-  if (!g_p4_c96 || a.Wout != 8 || a.Cout % 96 || a.M % GNW_BN || ITSD_P4_M16 < 2) return false;
+  if (!g_p4_c96 || a.Wout != 8 || a.Cout % 96 || a.M % GNW_BN) return false;
   const long long npt = a.M / GNW_BN, G = g_num_cus;
   const long long t96 = npt * (a.Cout / 96), r96 = (t96 + G - 1) / G;
   if (a.Cout % CONV_BM) return true;
@@ -4054,7 +3877,7 @@ static bool p5_selected(const ConvArgs& a) {
 // The ResBlock's 1x1 shortcut as extra K slices of its block2 conv on p5 (ConvArgs sc_*): the (S, S2) 3x3 /
 // shortcut slice counts minimising ceil(items / CUs) x the slower slice + the combine, in chunk-times (a 3x3
 // chunk = 1; a shortcut chunk ~0.4: 4 of its 36 k-steps, the same staging; prologue / epilogue 1.5); folded
-// where that beats the unfolded plan plus the standalone 1x1 launch it replaces (ITSD_P5_SC_LAUNCH = 5 chunk-times: a
+// where that beats the unfolded plan plus the standalone 1x1 launch it replaces (P5_SC_LAUNCH = 5 chunk-times: a
 // 10-20 us launch with its gap; 3 left the 32x32 shortcuts at N = 32, the 8x8 ones at N = 64 and the 4x4 ones at N = 256
 // unfolded, 0.5-1.1 % slower steps, profiles/r05/p5_sc_launch_cost_r05aq.txt), or always with g_p5_sc = 2. Returns S2
 // (0: not folded) and the S to run with.
@@ -4081,7 +3904,7 @@ static P5Plan p5_plan(const ConvArgs& a) {
     if (cb == 64 && (!g_p5_c64 || a.Wout > 8 || a.Cout % 64)) continue;
     if (cb == 128 && g_p5_c64 == 2 && a.Wout <= 8 && a.Cout % 64 == 0) continue;
     const int tiles = ptiles * (a.Cout / cb);
-    const double fc = cb == 128 ? 1.0 : ITSD_P5_C64_CHUNK;
+    const double fc = cb == 128 ? 1.0 : P5_C64_CHUNK;
     auto cost = [&](int s, int s2) {
       const double waves = std::ceil((double)tiles * (s + s2) / g_num_cus);
       const double c3 = std::ceil((double)nch / s) * fc + 1.5, c1 = s2 ? 0.4 * std::ceil((double)nchx / s2) + 1.5 : 0.0;
@@ -4091,7 +3914,7 @@ static P5Plan p5_plan(const ConvArgs& a) {
     p.cb = cb;
     p.tiles = tiles;
     p.s = ws ? p5_split(a, tiles, nch, cb, fc) : 1;
-    p.cost = cost(p.s, 0) + (sc ? ITSD_P5_SC_LAUNCH : 0.0);  // (unfolded: the shortcut's own launch besides)
+    p.cost = cost(p.s, 0) + (sc ? P5_SC_LAUNCH : 0.0);  // (unfolded: the shortcut's own launch besides)
     if (sc && (long long)tiles * 4 <= kTicketCap) {
       double bf = 1e30;
       int bs = 0, bs2 = 0;
@@ -4313,7 +4136,7 @@ static void launch_p5(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
   else ITSD_GO_W(conv3x3_gn_p5_kernel<32>, conv3x3_gn_p5_kernel<16>, conv3x3_gn_p5_kernel<8>);
 }
 
-static void launch_stream1x1(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+static hipError_t launch_stream1x1(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
   const int Cin = a.C1 + a.C2;
 #define ITSD_S1(NS)                                                 \
   if (Cin == 128) ITSD_GO((conv1x1_stream_kernel<128, NS>));        \
@@ -4321,12 +4144,17 @@ static void launch_stream1x1(const ConvArgs& a, const ConvPlan& p, hipStream_t s
   else if (Cin == 384) ITSD_GO((conv1x1_stream_kernel<384, NS>));   \
   else if (Cin == 512) ITSD_GO((conv1x1_stream_kernel<512, NS>));   \
   else ITSD_GO((conv1x1_stream_kernel<640, NS>));
-  if (g_conv1x1 == 2) {
+  if (g_conv1x1 == 2) {  // the 7-stage ring: instantiated in diagnostic builds only
+#ifdef ITSD_DIAG
     ITSD_S1(7)
-  } else {
-    ITSD_S1(4)
+    return hipSuccess;
+#else
+    return hipErrorInvalidValue;
+#endif
   }
+  ITSD_S1(4)
 #undef ITSD_S1
+  return hipSuccess;
 }
 
 // Runs the plan plan_conv made for these arguments (api.hip resolves both once per pass).
@@ -4370,7 +4198,9 @@ hipError_t launch_conv(const ConvArgs& a0, const ConvPlan& p, hipStream_t s) {
       if (p.gn_segs == 1) ITSD_GO(conv3x3_gn_kernel<1>);
       else ITSD_GO(conv3x3_gn_kernel<2>);
       break;
-    case ConvKernel::STREAM1X1: launch_stream1x1(a, p, s); break;
+    case ConvKernel::STREAM1X1:
+      if (launch_stream1x1(a, p, s) != hipSuccess) return hipErrorInvalidValue;
+      break;
     case ConvKernel::SMALL: ITSD_GO(conv_small<false>); break;
     // (3- / 4-stage rings at one block a CU measured 8-30 % slower for the sub-pixel phases and were removed in
     // round 5, profiles/r04/census_archC_2N64_conv_variant*.txt)

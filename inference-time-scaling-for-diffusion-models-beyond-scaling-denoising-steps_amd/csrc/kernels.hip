@@ -383,41 +383,9 @@ __device__ __forceinline__ void attn_out_tile(const f32x16& acc, const bf16_t* x
     v[4 * g + 3] = r3; v[16 + 4 * g + 3] = r3 * r3;
   }
 #pragma unroll
-  for (int gp = 0; gp < 4; gp += 2) {
-    u32x4 o;
-#pragma unroll
-    for (int d = 0; d < 2; ++d) {
-      const auto sw = __builtin_amdgcn_permlane32_swap(wv[gp][d], wv[gp + 1][d], false, false);
-      o[d] = sw[0];
-      o[2 + d] = sw[1];
-    }
-    *(u32x4*)(out + (size_t)tk * C + c0 + 8 * (gp + hh)) = o;
-  }
+  for (int gp = 0; gp < 4; gp += 2) *(u32x4*)(out + (size_t)tk * C + c0 + 8 * (gp + hh)) = epi_pack(wv, gp);
   if (sp) {  // the tile's 32 lanes: butterfly (lanes rl < 16 end with the sums, the others with the squares)
-    auto xchg = [](float xf, auto wc) {
-      constexpr int wd = decltype(wc)::value;
-      const int xi = __builtin_bit_cast(int, xf);
-      int r;
-      if constexpr (wd == 1) r = __builtin_amdgcn_update_dpp(0, xi, 0xB1, 0xF, 0xF, false);
-      else if constexpr (wd == 2) r = __builtin_amdgcn_update_dpp(0, xi, 0x4E, 0xF, 0xF, false);
-      else if constexpr (wd == 8) r = __builtin_amdgcn_update_dpp(0, xi, 0x128, 0xF, 0xF, false);
-      else r = __builtin_amdgcn_ds_swizzle(xi, 0x1F | (wd << 10));
-      return __builtin_bit_cast(float, r);
-    };
-    auto halve = [&](auto wc) {
-      constexpr int wd = decltype(wc)::value;
-      const bool up = (rl & wd) != 0;
-#pragma unroll
-      for (int ii = 0; ii < wd; ++ii) {
-        const float lo = v[ii], hi = v[ii + wd];
-        v[ii] = (up ? hi : lo) + xchg(up ? lo : hi, wc);
-      }
-    };
-    halve(std::integral_constant<int, 16>{});
-    halve(std::integral_constant<int, 8>{});
-    halve(std::integral_constant<int, 4>{});
-    halve(std::integral_constant<int, 2>{});
-    halve(std::integral_constant<int, 1>{});
+    stat_butterfly32(v, rl);
     const int e = rl & 15;
     sp[(rl >> 4) * sps + 8 * (e >> 2) + 4 * hh + (e & 3)] = v[0];
   }
@@ -425,12 +393,9 @@ __device__ __forceinline__ void attn_out_tile(const f32x16& acc, const bf16_t* x
 
 // (round 4's 4-images-a-block form for the 4x4 middle block, S = 16, measured slower than the unfused ops
 // at N = 32 and equal at N = 256, was removed in round 5)
-#ifndef ITSD_ATTN_PF
-#define ITSD_ATTN_PF 8
-#endif
 template <int C>
 __global__ __launch_bounds__(512, 1) void attn_block_kernel(AttnBlockArgs a) {
-  constexpr int S = 64, KS = C / 16, CB = C / 32, CBW = CB / 4, NU = 2 * CB / 8, PF = ITSD_ATTN_PF;
+  constexpr int S = 64, KS = C / 16, CB = C / 32, CBW = CB / 4, NU = 2 * CB / 8, PF = 8;
   static_assert(C % 128 == 0, "C");
   // hn [64][C] | V'^T [C][64] | T [64][C], later the scores S [64][64 + 4] fp32 and P [64][64] | group (mean, rstd) |
   // the two token blocks' statistics
@@ -681,12 +646,9 @@ __global__ __launch_bounds__(512, 1) void attn_block_kernel(AttnBlockArgs a) {
 // overlap) it is a multiple of 12 whatever G earlier launches used, and a block's target -- the next multiple
 // of 12 above the value its own add returned -- is reached exactly when the launch's G blocks have added.
 // Waiting blocks need the whole grid resident: the host launches it only when n * G <= CUs (one 512-thread block per CU).
-#ifndef ITSD_ATTN_SPLIT_PF
-#define ITSD_ATTN_SPLIT_PF 8
-#endif
 template <int C, int G>
 __global__ __launch_bounds__(512, 1) void attn_block_split_kernel(AttnBlockArgs a) {
-  constexpr int S = 64, KS = C / 16, CB = C / 32, CBg = CB / G, CW = CBg * 32, PF = ITSD_ATTN_SPLIT_PF;
+  constexpr int S = 64, KS = C / 16, CB = C / 32, CBg = CB / G, CW = CBg * 32, PF = 8;
   static_assert(CB % G == 0 && C % 128 == 0 && 12 % G == 0, "G divides the channel blocks and 12");
   constexpr int QROW = CW * 2 + 16;  // T_g row (bytes): padded so 16-B reads of 16 rows are conflict-free
   constexpr int R_VT = S * C * 2, R_T = R_VT + CW * 128, R_SM = R_T + S * QROW;
@@ -1808,10 +1770,7 @@ __global__ __launch_bounds__(256) void tail2_kernel(TailArgs a) {
 // ds_read_b128 group ({0-3, 12-15, 20-27}, ...: 8 pixels of one k-group + 8 of the next) then lands on 16 distinct
 // 16-B slots, the two k-groups on opposite slot parities (2C + 16, one unit odd, put pixel m + 1 of one k-group on
 // pixel m's slot of the other: 6.8e6 bank-conflict cycles a launch at N = 256, profiles/r05/pmc_dispatch_table_r05ae.txt)
-#ifndef ITSD_TAIL_PAD32
-#define ITSD_TAIL_PAD32 1  // (0: 2C + 16, A/B builds)
-#endif
-__host__ __device__ constexpr int tail_pst(int C) { return 2 * C + (ITSD_TAIL_PAD32 ? 32 : 16); }
+__host__ __device__ constexpr int tail_pst(int C) { return 2 * C + 32; }
 
 template <int TM_PX, int NTH, int EPI = 0>
 __global__ __launch_bounds__(NTH, 2) void tail_mfma_kernel(TailArgs a) {

@@ -141,6 +141,10 @@ def test_shipped_library_holds_only_product_kernels():
                  b"conv3x3_gn_pws_kernel", b"conv_pipe_wide", b"itsd_debug_stamps",
                  # round 5: the dropped 16x16x32 p4 form, p4 at 64x64, the 4-image AttnBlock, 3/4-stage pipes
                  b"conv3x3_gn_p4_kernelILi32ELi0ELb1", b"conv3x3_gn_p4_kernelILi64", b"attn_block_kernelILi512ELi4",
-                 b"conv_pipeItLi3", b"conv_pipeItLi4", b"tail_mfma_kernelILi64"):
+                 b"conv_pipeItLi3", b"conv_pipeItLi4", b"tail_mfma_kernelILi64",
+                 # the 7-stage streaming 1x1 ring (conv1x1 = 2, which the shipped ABI refuses): diagnostic builds only
+                 b"conv1x1_stream_kernelILi128ELi7", b"conv1x1_stream_kernelILi256ELi7",
+                 b"conv1x1_stream_kernelILi384ELi7", b"conv1x1_stream_kernelILi512ELi7",
+                 b"conv1x1_stream_kernelILi640ELi7"):
         assert name not in blob, name
     assert b"conv3x3_gn_p4_kernel" in blob

@@ -1,17 +1,22 @@
 """Per-kernel register / scratch / spill table from hipcc -Rpass-analysis=kernel-resource-usage
-(compile-time check, no GPU).  python tools/regs.py [filter]  (builds conv.hip / kernels.hip device-only)"""
-import os, re, subprocess, sys
+(compile-time check, no GPU).  python tools/regs.py [filter] [file.hip ...]  (default conv.hip; each file is
+built device-only with build.py's flags for it)"""
+import importlib.util, os, re, subprocess, sys, tempfile
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(HERE, "inference-time-scaling-for-diffusion-models-beyond-scaling-denoising-steps_amd")
+spec = importlib.util.spec_from_file_location("itsd_build", os.path.join(PKG, "build.py"))
+build = importlib.util.module_from_spec(spec)
+spec.loader.exec_module(build)
 flt = sys.argv[1] if len(sys.argv) > 1 else ""
 srcs = [a for a in sys.argv[2:]] or ["conv.hip"]
 for s in srcs:
-    cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-I", os.path.join(PKG, "csrc"),
-           "-I", os.path.join(HERE, "include"), "-munsafe-fp-atomics", "--cuda-device-only", "-c",
-           os.path.join(PKG, "csrc", s), "-o", "/tmp/_regs.o", "-Rpass-analysis=kernel-resource-usage"]
-    if s == "conv.hip":
-        cmd.append("-fno-slp-vectorize")
-    r = subprocess.run(cmd, capture_output=True, text=True)
+    src = os.path.join(build.CSRC, s)
+    with tempfile.TemporaryDirectory() as tmp:
+        cmd = [build.HIPCC] + build.flags_for(src) + ["--cuda-device-only", "-c", src, "-o", os.path.join(tmp, "regs.o"),
+                                                       "-Rpass-analysis=kernel-resource-usage"]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        sys.exit(r.stderr)
     cur = None
     rows = {}
     for line in r.stderr.splitlines():
@@ -26,4 +31,5 @@ for s in srcs:
     for k, v in rows.items():
         if flt in k:
             print(f"{k[:70]:70s} vgpr {v.get('VGPRs',0):3d} agpr {v.get('AGPRs',0):3d} scratch {v.get('ScratchSize [bytes/lane]',0):4d} "
-                  f"vspill {v.get('VGPRs Spill',0):3d} sspill {v.get('SGPRs Spill',0):3d} sgpr {v.get('SGPRs',0):3d} occ {v.get('Occupancy [waves/SIMD]',0)}")
+                  f"vspill {v.get('VGPRs Spill',0):3d} sspill {v.get('SGPRs Spill',0):3d} sgpr {v.get('TotalSGPRs',0):3d} "
+                  f"lds {v.get('LDS Size [bytes/block]',0):6d} occ {v.get('Occupancy [waves/SIMD]',0)}")
