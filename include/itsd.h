@@ -23,6 +23,9 @@
  *   itsd_sampler_predict_x0      <- (no reference counterpart) the x_0 estimate of a half-denoised state, what a
  *                                   verifier can score mid-trajectory: the branching PathSearch its docstring
  *                                   describes (search/search_algorithm.py:238-250; its code, :307-312, is a placeholder)
+ *   itsd_sampler_set_trace       <- (no reference counterpart) a score trace: every step of an x0-form run leaves each
+ *                                   image's x_0 moments (sum, sum of squares, min, max), what the image-statistics
+ *                                   verifiers need, at no extra UNet evaluation
  *   itsd_branch                  <- (no reference counterpart) gather the surviving paths and re-noise them
  *   itsd_es_candidates / _es_step / _es_workspace_bytes
  *                                <- GradientBasedSearch (search/search_algorithm.py:343-438) without autograd: the
@@ -170,6 +173,28 @@ int itsd_set_schedule_x0(itsd_unet* u, const itsd_x0_schedule* schedule);
  * captured under one form is never replayed under the other (the form is part of the cache key). */
 int itsd_sampler_run(itsd_unet* u, float* x, const int32_t* labels, int n, int t_begin, int t_end,
                      uint64_t seed, int64_t noise_offset, const float* noise, uint32_t flags, void* stream);
+
+/* Attach (trace != NULL) or detach a score trace. trace: device fp64 [rows][stride][4], caller-owned,
+ * 32-byte aligned; rows must equal T_sched of the installed x0-form schedule, stride >= the n of every run.
+ * While attached, step k of itsd_sampler_run on images i < n writes
+ * trace[k][i] = (sum x0, sum x0^2, min x0, max x0) over the image's 3 H W elements,
+ * x0 the estimate that step used (clipped iff clip_x0); rows not run and images >= n are not written.
+ * x after the run is bit-identical to the untraced run.
+ * CFG: the x0 of the guided step, for the n candidates. Summation: fp32 without contraction inside a tail block (the
+ * thread's items in order, a 6-level lane butterfly, the wave partials in wave order; min / max through the same
+ * tree), one plain store of four floats a block, then each image's blocks in block order in fp64 by a second small
+ * launch that reads the row from the device step counter -- it is part of the step program, so one captured step
+ * graph serves every row. No atomics: a row entry is a function of the candidate alone.
+ * The trace pointer and stride are part of the step graph's cache key: a graph captured untraced is never replayed
+ * traced, or the reverse, and detaching brings the earlier graph back without a new capture. Installing a schedule
+ * (either call) detaches. itsd_sampler_predict_x0 and itsd_verify_denoise ignore the trace.
+ * itsd_unet_query(u, "trace", ..) answers 0 | 1.
+ * ITSD_ERR_INVALID with a message naming this function, before any HIP call: a null handle; attaching with no
+ * x0-form schedule installed (the ancestral form has no a0 / b0 rows; ddim with steps = T, eta = 1 is its x0-form
+ * equivalent), rows != T_sched, stride < 1, a pointer that is not 32-byte aligned. At run time itsd_sampler_run
+ * answers ITSD_ERR_INVALID for n > stride and for a tail geometry whose blocks would straddle two images (the generic
+ * tail kernel with H W % 256 != 0), before any launch. */
+int itsd_sampler_set_trace(itsd_unet* u, double* trace, int rows, int stride);
 
 /* x0[n,3,H,W] = clip(a0*x - b0*eps(x, t[, labels]), -1, 1): the sampler's own forward at step t
  * (guided for CFG) with the x0 epilogue; x is not modified. Needs itsd_set_schedule (t < T_sched) or
@@ -321,7 +346,7 @@ int itsd_set_option(const char* key, int value);
 
 /* Introspection of a handle (no device work): "graph_captures" (step graphs captured and
  * instantiated so far; a search replays one graph across all its rounds), "max_batch",
- * "T_sched" (timesteps, or the rows K of an x0-form schedule), "sched_form" (0 ancestral, 1 x0-form), "ws_bytes"
+ * "T_sched" (timesteps, or the rows K of an x0-form schedule), "sched_form" (0 ancestral, 1 x0-form), "trace" (1 while a score trace is attached), "ws_bytes"
  * (activation arena), "ops" (program length); and, synchronising the
  * handle's stream, "status" = the in-kernel hand-off status word of the last forward / sampler run
  * (0 ok; bit 0: attn_block_split_kernel's wait exhausted its bound, bit 1: conv3x3_gn_p5_kernel's shared split-K

@@ -52,6 +52,7 @@ hipError_t launch_gn_coef(const GNArgs&, int, float*, hipStream_t);
 hipError_t launch_head_mfma(const HeadArgs&, hipStream_t);
 hipError_t launch_tail_mfma(const TailArgs&, hipStream_t);
 bool tail_mfma_ok(int H, int W, int C);
+bool tail_block_straddles(int H, int W, int C);
 int g_io_mfma = 1;  // bf16 head / tail on MFMA (itsd_set_option "io_mfma", read at create)
 int g_small_gn = 1;  // conv_small writes its consumer GroupNorm's output (itsd_set_option "small_gn"): 0 off, 1 on
 hipError_t launch_noise(float*, const float*, int, long long, float, unsigned long long, unsigned, long long,
@@ -171,7 +172,8 @@ struct Arena {
 // staged through handle-owned buffers and the seed, noise offset and clip step live in device
 // memory (RunParams), so every round of a search replays one graph.
 struct GraphEntry {
-  std::tuple<int, bool, const float*, int, int> key;  // (n, labels, noise, option generation, schedule form)
+  // (n, labels, noise, option generation, schedule form, trace, trace stride)
+  std::tuple<int, bool, const float*, int, int, const double*, int> key;
   hipGraphExec_t exec = nullptr;
 };
 
@@ -229,6 +231,11 @@ struct itsd_unet {
   // per-block partial pairs [max_batch][H W / 64 blocks at most][2]
   float* vd_xt = nullptr;
   float* vd_part = nullptr;
+  // the score trace (itsd_sampler_set_trace): the caller's buffer [trace_rows][trace_stride][4] fp64, null while
+  // detached, and the tail's per-block partials [max_batch][H W / 64 blocks at most][4], allocated at the first attach
+  double* trace = nullptr;
+  int trace_rows = 0, trace_stride = 0;
+  float* tr_part = nullptr;
   long long graph_captures = 0;  // step graphs captured + instantiated (itsd_unet_query)
   void* zero_page = nullptr;  // 256 KiB of zeros (conv DMA source for padding, conv.hip zero_of_block)
   float* splitk_ws = nullptr;  // split-K partial tiles (shared by all convs: they run in stream order)
@@ -1331,10 +1338,12 @@ void clear_graphs(itsd_unet* u) {
   u->graphs.clear();
 }
 
-// Either schedule call starts here: no step graph and no table of the previous schedule, of either form, survives
-// (T_sched = 0 until the new one is complete, so a failed call leaves the handle without a schedule).
+// Either schedule call starts here: no step graph, no table of the previous schedule, of either form, and no attached
+// trace survives (T_sched = 0 until the new one is complete, so a failed call leaves the handle without a schedule).
 void drop_schedule(itsd_unet* u) {
   clear_graphs(u);
+  u->trace = nullptr;
+  u->trace_rows = u->trace_stride = 0;
   hipFree(u->coeff1); hipFree(u->coeff2); hipFree(u->sqrt_var); hipFree(u->xrow); hipFree(u->temb_table);
   u->coeff1 = u->coeff2 = u->sqrt_var = u->xrow = u->temb_table = nullptr;
   u->T_sched = 0;
@@ -1352,6 +1361,7 @@ int check_batch(itsd_unet* u, int n) {
 // itsd_verify_denoise's two scratch buffers (itsd_unet::vd_xt, vd_part): the smallest tail block is 64 pixels
 size_t vd_xt_bytes(const itsd_unet* u) { return (size_t)u->d.max_batch * 3 * u->H * u->H * 4; }
 size_t vd_part_bytes(const itsd_unet* u) { return (size_t)u->d.max_batch * ((u->H * u->H + 63) / 64) * 2 * 4; }
+size_t tr_part_bytes(const itsd_unet* u) { return 2 * vd_part_bytes(u); }  // (four floats a block)
 
 // The two pass shapes. forward: one time-embedding row an image (proj_buf, from temb_rows), the batch as given, the
 // tail writes eps to eps_out.
@@ -1393,11 +1403,14 @@ int leave_stream(itsd_unet* u, hipStream_t cs) {
   return ITSD_OK;
 }
 
-// The step graph of (n, labels present, noise pointer, option generation, schedule form): the cached one, or one step of c (the
-// program, then the step counter's decrement) captured on u->stream, instantiated and cached -- 4 entries, the oldest
-// out. A failed capture is ended and its graph destroyed before the error is returned.
+// The step graph of (n, labels present, noise pointer, option generation, schedule form, trace pointer and stride):
+// the cached one, or one step of c (the program -- the trace's finalize launch rides behind the tail -- then the step
+// counter's decrement) captured on u->stream, instantiated and cached -- 4 entries, the oldest out. The trace is in the
+// key because its pointer is baked into the captured launches: a graph captured untraced is never replayed traced. A
+// failed capture is ended and its graph destroyed before the error is returned.
 int step_graph(itsd_unet* u, const RunCtx& c, int n, bool labels, const float* noise, hipGraphExec_t* exec) {
-  const auto key = std::make_tuple(n, labels, noise, itsd::g_option_gen, u->sched_form);
+  const auto key = std::make_tuple(n, labels, noise, itsd::g_option_gen, u->sched_form, (const double*)u->trace,
+                                   u->trace_stride);
   for (auto& g : u->graphs)
     if (g.key == key) { *exec = g.exec; return ITSD_OK; }
   hipStream_t s = u->stream;
@@ -1611,6 +1624,7 @@ int itsd_unet_query(const itsd_unet* u, const char* key, int64_t* value) {
   else if (!std::strcmp(key, "max_batch")) *value = u->d.max_batch;
   else if (!std::strcmp(key, "T_sched")) *value = u->T_sched;
   else if (!std::strcmp(key, "sched_form")) *value = u->sched_form;
+  else if (!std::strcmp(key, "trace")) *value = u->trace ? 1 : 0;
   else if (!std::strcmp(key, "ws_bytes")) *value = (int64_t)u->ws_bytes;
   else if (!std::strcmp(key, "ops")) *value = (int64_t)u->ops.size();
   else if (!std::strcmp(key, "status")) {  // synchronous: the in-kernel hand-off status word of the last forward / run
@@ -1688,6 +1702,7 @@ int itsd_unet_destroy(itsd_unet* u) {
   hipFree(u->attn_sync);
   hipFree(u->vd_xt);
   hipFree(u->vd_part);
+  hipFree(u->tr_part);
   if (u->stream) hipStreamDestroy(u->stream);
   if (u->ev_in) hipEventDestroy(u->ev_in);
   if (u->ev_out) hipEventDestroy(u->ev_out);
@@ -1795,6 +1810,14 @@ int itsd_sampler_run(itsd_unet* u, float* x, const int32_t* labels, int n, int t
   if (u->cfg && !labels) return fail(ITSD_ERR_INVALID, "CFG sampler needs labels");
   CHK(check_batch(u, n));
   if (t_begin >= u->T_sched || t_end < 0 || t_end > t_begin) return fail(ITSD_ERR_INVALID, "bad step range");
+  if (u->trace) {  // (attached under this x0-form schedule: itsd_sampler_set_trace, drop_schedule)
+    if (n > u->trace_stride)
+      return fail(ITSD_ERR_INVALID, "itsd_sampler_run: batch " + std::to_string(n) + " > the attached trace's stride " +
+                                        std::to_string(u->trace_stride));
+    if (u->tail_wmf == SIZE_MAX && tail_block_straddles(u->H, u->H, u->acts[u->tail_in].C))
+      return fail(ITSD_ERR_INVALID, "itsd_sampler_run: no score trace at this tail geometry (a 256-pixel block of the "
+                                    "generic tail kernel would straddle two images: H W % 256 != 0)");
+  }
   hipStream_t cs = (hipStream_t)stream;
   hipStream_t s = u->stream;
   CHK(enter_stream(u, cs));
@@ -1811,6 +1834,10 @@ int itsd_sampler_run(itsd_unet* u, float* x, const int32_t* labels, int n, int t
   if (u->sched_form) {  // rows, not timesteps: d_t, the Philox stream id and the injected-noise index are the row
     for (int i = 0; i < 5; ++i) t.xrow[i] = u->xrow + (size_t)i * u->T_sched;
     t.clip_x0 = u->clip_x0;
+    if (u->trace) {
+      t.step_mode = 5;
+      t.tpart = u->tr_part; t.trace = u->trace; t.trace_rows = u->trace_rows; t.trace_stride = u->trace_stride;
+    }
   }
   t.noise = noise; t.run = u->d_run; t.nan_flag = u->d_nan;
 
@@ -1838,6 +1865,31 @@ int itsd_sampler_run(itsd_unet* u, float* x, const int32_t* labels, int n, int t
     if (flag[1]) return fail(ITSD_ERR_HANDOFF, handoff_msg(flag[1]));
     if (flag[0]) return fail(ITSD_ERR_NAN, "nan in tensor.");
   }
+  return ITSD_OK;
+}
+
+int itsd_sampler_set_trace(itsd_unet* u, double* trace, int rows, int stride) {
+  if (!u) return fail(ITSD_ERR_INVALID, "itsd_sampler_set_trace: null handle");
+  if (!trace) {  // detach: the graphs captured untraced are still cached under their own key
+    u->trace = nullptr;
+    u->trace_rows = u->trace_stride = 0;
+    return ITSD_OK;
+  }
+  if (!u->T_sched || !u->sched_form)
+    return fail(ITSD_ERR_INVALID, "itsd_sampler_set_trace: no x0-form schedule installed (itsd_set_schedule_x0; the "
+                                  "ancestral form has no x0 rows)");
+  if (rows != u->T_sched)
+    return fail(ITSD_ERR_INVALID, "itsd_sampler_set_trace: rows = " + std::to_string(rows) + " != T_sched = " +
+                                      std::to_string(u->T_sched));
+  if (stride < 1) return fail(ITSD_ERR_INVALID, "itsd_sampler_set_trace: stride = " + std::to_string(stride) + " < 1");
+  if ((uintptr_t)trace % 32) return fail(ITSD_ERR_INVALID, "itsd_sampler_set_trace: trace is not 32-byte aligned");
+  if (!u->tr_part) {
+    HIPCHK(hipSetDevice(u->device));
+    HIPCHK(hipMalloc(&u->tr_part, tr_part_bytes(u)));
+  }
+  u->trace = trace;
+  u->trace_rows = rows;
+  u->trace_stride = stride;
   return ITSD_OK;
 }
 
@@ -2262,6 +2314,8 @@ int itsd_unet_poison(itsd_unet* u, void* stream) {
   // itsd_verify_denoise's scratch (once it exists): the call stores every element it reads
   if (u->vd_xt) HIPCHK(hipMemsetAsync(u->vd_xt, 0xFF, vd_xt_bytes(u), u->stream));
   if (u->vd_part) HIPCHK(hipMemsetAsync(u->vd_part, 0xFF, vd_part_bytes(u), u->stream));
+  // the traced step's per-block partials (once they exist): the tail stores every one its finalize launch reads
+  if (u->tr_part) HIPCHK(hipMemsetAsync(u->tr_part, 0xFF, tr_part_bytes(u), u->stream));
   u->last_forward_n = 0;  // (the tail input is gone: itsd_unet_representation refuses until the next forward)
   return leave_stream(u, cs);
 }

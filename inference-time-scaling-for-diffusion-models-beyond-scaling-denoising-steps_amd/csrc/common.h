@@ -392,8 +392,8 @@ struct TailArgs {
   float guide_w1;       // (1 + w) computed in double then cast, as the reference's scalar
   // mode
   int step_mode;        // 0: write eps NCHW; 1: sampler update of x in place; 2: x0_out = clip(a0 x - b0 eps) (x read only);
-                        // 3: the x0-form update of x in place (rows of xrow, below); 4: the denoising-error sums (last
-                        // fields, below)
+                        // 3: the x0-form update of x in place (rows of xrow, below); 4: the denoising-error sums;
+                        // 5: step 3 plus the x0 moments of every image (last fields, below)
   float* eps_out;       // NCHW [n][3][H][W]
   float* x;             // NCHW [n][3][H][W]
   const int* tsel;      // current step t (device)
@@ -421,10 +421,19 @@ struct TailArgs {
   // vpart[blockIdx.x] (blocks are image-major and never straddle two images) and tail_sse_finalize_kernel sums each
   // image's pairs in block order in fp64 into vsse[n][2]. eps_out, when non-null, receives the unguided
   // eps [1 or 2][n][3][H][W] (cond, then uncond). x is not read.
+  // step_mode 5 (itsd_sampler_run with a score trace attached, itsd_sampler_set_trace): step_mode 3 on x, bit for bit,
+  // and each block stores (sum x0, sum x0^2, min x0, max x0) of its output elements -- x0 the value the step used,
+  // clipped iff clip_x0 -- as four fp32 at tpart[blockIdx.x] (blocks are image-major and never straddle two images);
+  // tail_mom_finalize_kernel folds each image's blocks in block order in fp64 into
+  // trace[(*tsel * trace_stride + img) * 4 + 0..3], for a row *tsel in [0, trace_rows).
+  // Its operands share the storage of step_mode 4's, which it never reads (and the reverse), and trace_stride sits in
+  // what was padding: the struct keeps its size and offsets. The struct is the kernels' argument block, and a larger
+  // one changed the register allocation of the existing tail_mfma_kernel instantiations.
   unsigned long long vseed;
-  unsigned vstream;
-  float* vpart;
-  double* vsse;
+  union { unsigned vstream; int trace_rows; };
+  int trace_stride;
+  union { float* vpart; float* tpart; };
+  union { double* vsse; double* trace; };
 };
 
 constexpr int kBranchChunk = 256;  // parent-table rows a branch_kernel launch carries in its arguments (1 KiB)

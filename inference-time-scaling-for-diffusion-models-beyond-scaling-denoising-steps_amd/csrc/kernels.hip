@@ -1419,7 +1419,7 @@ __device__ __forceinline__ float philox_normal(unsigned long long seed, unsigned
 // tail = GN -> Swish -> Conv2d(C, 3, 3, padding=1) (Model.py:252-256, 282). The GN+Swish
 // output g is produced by groupnorm_kernel (tail_mfma_kernel applies it itself); the three kernels below do the
 // 3-output conv per pixel and hand each output element's eps to tail_finish (tail_sse_item for the last), which ends in
-// one of five ways:
+// one of six ways:
 //   eps  (TailArgs::step_mode 0, the forward API)  eps_out = eps
 //   step (step_mode 1)  the ancestral update of Diffusion.py:67-71,96-100 in place on x:
 //          mean = coeff1[t]*x - coeff2[t]*eps ;  x = mean + sqrt(var[t]) * z  (z = 0 at t = 0; injected or Philox),
@@ -1445,8 +1445,14 @@ __device__ __forceinline__ float philox_normal(unsigned long long seed, unsigned
 //          of (image, label, z) alone, whatever the batch or the image's place in it. eps_out (debug, NULL in
 //          production) receives the unguided eps [1 or 2][n][3][H][W].
 // CFG: eps = (1+w) eps_c - w eps_u (DiffusionCondition.py:85) with the unconditional
-// branch at image index img + n of g (guided before tail_finish, in the first four modes).
-// EPI, the kernels' template parameter, names the instantiation: 0 eps / step, 1 x0, 2 x0 step, 3 sse.
+// branch at image index img + n of g (guided before tail_finish, in every mode but sse).
+//   x0 step + moments (step_mode 5, its own instantiation)  the x0 step, the same expressions in the same order on the
+//          same x (bit-identical new x), and each output element's x0 -- the value the step used, clipped iff
+//          clip_x0; CFG: of the guided step, the n candidates only -- added to the thread's (sum, sum of squares, min,
+//          max), reduced by tail_mom_block (tail_sse_block's tree) into tpart[blockIdx.x][4]; tail_mom_finalize_kernel
+//          folds each image's blocks in block order in fp64 into row *tsel of the caller's trace. No atomics.
+// EPI, the kernels' template parameter, names the instantiation: 0 eps / step, 1 x0, 2 x0 step, 3 sse, 4 x0 step +
+// moments.
 __device__ __forceinline__ float tail_x0(float a0, float b0, float xv, float e) {
 #pragma clang fp contract(off)
   const float v = a0 * xv - b0 * e;
@@ -1467,12 +1473,12 @@ struct TailStep {
 template <int EPI>
 __device__ __forceinline__ TailStep tail_step_load(const TailArgs& a) {
   TailStep s;
-  if (EPI == 2 || (EPI == 0 && a.step_mode)) {
+  if (EPI == 2 || EPI == 4 || (EPI == 0 && a.step_mode)) {
     s.t = *a.tsel;
     s.seed = a.run->seed;
     s.noise_offset = a.run->noise_offset;
     s.clip_at = a.run->clip_at;
-    if constexpr (EPI == 2) {
+    if constexpr (EPI == 2 || EPI == 4) {
       s.a0 = a.xrow[0][s.t];
       s.b0 = a.xrow[1][s.t];
       s.c1 = a.xrow[2][s.t];
@@ -1499,18 +1505,33 @@ __device__ __forceinline__ size_t tail_offset(int img, int y0, int opx, int oc, 
   return ((size_t)img * 3 + oc) * (H * W) + rem;
 }
 
+// The moments epilogue's running (sum x0, sum x0^2, min x0, max x0) of a thread, a wave or a block. A thread without
+// items keeps the neutral element.
+struct TailMom {
+  float s = 0.f, q = 0.f, lo = INFINITY, hi = -INFINITY;
+};
+
 // One output element: its (guided) eps e, its NCHW offset o, its x value xv (tail_x) and the step's scalars. Returns
-// whether the step's new x is NaN (false in the other two modes).
+// whether the step's new x is NaN (false in the other two modes). EPI 4 is EPI 2's step, expression for expression,
+// and adds the x0 the step used to the thread's moments mom (fp32, no contraction, the thread's items in call order).
 template <int EPI>
-__device__ __forceinline__ bool tail_finish(const TailArgs& a, const TailStep& s, size_t o, float xv, float e) {
+__device__ __forceinline__ bool tail_finish(const TailArgs& a, const TailStep& s, size_t o, float xv, float e,
+                                            TailMom* mom = nullptr) {
 #pragma clang fp contract(off)
   if constexpr (EPI == 1) {
     a.x0_out[o] = tail_x0(a.a0, a.b0, xv, e);
     return false;
   }
-  if constexpr (EPI == 2) {
+  if constexpr (EPI == 2 || EPI == 4) {
     float x0 = s.a0 * xv - s.b0 * e;
     if (a.clip_x0) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    if constexpr (EPI == 4) {
+      const float sq = x0 * x0;
+      mom->s = mom->s + x0;
+      mom->q = mom->q + sq;
+      mom->lo = fminf(mom->lo, x0);
+      mom->hi = fmaxf(mom->hi, x0);
+    }
     float xn = (s.c1 * x0) + (s.c2 * xv);
     if (s.sv != 0.f) {  // (one row a launch: uniform)
       const float z = a.noise ? a.noise[(size_t)s.t * a.n * 3 * (a.H * a.W) + o]
@@ -1584,6 +1605,37 @@ __device__ __forceinline__ void tail_sse_block(const TailArgs& a, float* scratch
   }
 }
 
+// The moments epilogue's block reduction, tail_sse_block's tree on four values: reached by every thread of the block
+// (NW waves), lane butterfly (sums by +, min / max by fminf / fmaxf), the wave partials through LDS (scratch: >= 4 NW
+// floats nothing reads any more), folded in wave order by thread 0, one plain store of the four floats.
+template <int NW>
+__device__ __forceinline__ void tail_mom_block(const TailArgs& a, float* scratch, TailMom m) {
+  m.s = wave_sum(m.s);
+  m.q = wave_sum(m.q);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    m.lo = fminf(m.lo, __shfl_xor(m.lo, o, 64));
+    m.hi = fmaxf(m.hi, __shfl_xor(m.hi, o, 64));
+  }
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) {
+    float* p = scratch + (threadIdx.x >> 6) * 4;
+    p[0] = m.s; p[1] = m.q; p[2] = m.lo; p[3] = m.hi;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float s = scratch[0], q = scratch[1], lo = scratch[2], hi = scratch[3];
+    for (int w = 1; w < NW; ++w) {
+      s += scratch[4 * w];
+      q += scratch[4 * w + 1];
+      lo = fminf(lo, scratch[4 * w + 2]);
+      hi = fmaxf(hi, scratch[4 * w + 3]);
+    }
+    float* p = a.tpart + (size_t)blockIdx.x * 4;
+    p[0] = s; p[1] = q; p[2] = lo; p[3] = hi;
+  }
+}
+
 // reference layout w[co][ci][ky][kx] -> wl[(tap*C + ci)*3 + co] (256 threads)
 __device__ __forceinline__ void tail_stage_weights(float* wl, const float* w, int C) {
   for (int i = threadIdx.x; i < 27 * C; i += 256) {
@@ -1653,6 +1705,17 @@ __global__ __launch_bounds__(256) void tail_kernel(TailArgs a) {
   }
   const TailStep st = tail_step_load<EPI>(a);
   bool bad = false;
+  if constexpr (EPI == 4) {  // (H W % 256 == 0 only, as EPI 3: every thread of the block is here)
+    TailMom mom;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const size_t o = ((size_t)img * 3 + c) * HW + rem;
+      bad |= tail_finish<EPI>(a, st, o, tail_x<EPI>(a, o), eps[c], &mom);
+    }
+    if (bad) atomicOr(a.nan_flag, 1);
+    tail_mom_block<4>(a, wl, mom);
+    return;
+  }
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     const size_t o = ((size_t)img * 3 + c) * HW + rem;
@@ -1734,6 +1797,29 @@ __global__ __launch_bounds__(256) void tail2_kernel(TailArgs a) {
       tail_sse_item(a, tail_offset(img, y0, opx, oc, H, W), img, a.b[oc] + s, a.b[oc] + su, qc, qu);
     }
     tail_sse_block<4>(a, wl, qc, qu);
+    return;
+  }
+  if constexpr (EPI == 4) {  // the step below, word for word, on threads 0..191; every thread reaches the reduction
+    TailMom mom;
+    if (tid < 192) {
+      const int opx = tid / 3, oc = tid - opx * 3;
+      float e = a.b[oc];
+      {
+        float s = 0.f;
+        for (int w = 0; w < 4; ++w) s += red[(w * 64 + opx) * 3 + oc];
+        e += s;
+      }
+      if (a.cfg) {
+#pragma clang fp contract(off)
+        float s = 0.f;
+        for (int w = 0; w < 4; ++w) s += red[((4 + w) * 64 + opx) * 3 + oc];
+        const float u = a.b[oc] + s;
+        e = a.guide_w1 * e - a.guide_w * u;
+      }
+      const size_t o = tail_offset(img, y0, opx, oc, H, W);
+      if (tail_finish<EPI>(a, tail_step_load<EPI>(a), o, tail_x<EPI>(a, o), e, &mom)) atomicOr(a.nan_flag, 1);
+    }
+    tail_mom_block<4>(a, wl, mom);
     return;
   }
   if (tid >= 192) return;
@@ -1904,6 +1990,24 @@ __global__ __launch_bounds__(NTH, 2) void tail_mfma_kernel(TailArgs a) {
     tail_sse_block<NW>(a, (float*)tsm, qc, qu);
     return;
   }
+  if constexpr (EPI == 4) {  // the loop below, word for word, with the thread's moments
+    TailMom mom;
+#pragma unroll
+    for (int k = 0; k < TIT; ++k) {
+      const int it = tid + NTH * k;
+      if (it >= TM_PX * 3) break;
+      const int opx = it / 3, oc = it - opx * 3;
+      float e = red[opx * 3 + oc] + a.b[oc];
+      if (a.cfg) {
+#pragma clang fp contract(off)
+        const float u = red[(TM_PX + opx) * 3 + oc] + a.b[oc];
+        e = a.guide_w1 * e - a.guide_w * u;
+      }
+      if (tail_finish<EPI>(a, st, tail_offset(img, y0, opx, oc, H, W), xpre[k], e, &mom)) atomicOr(a.nan_flag, 1);
+    }
+    tail_mom_block<NW>(a, (float*)tsm, mom);
+    return;
+  }
 #pragma unroll
   for (int k = 0; k < TIT; ++k) {
     const int it = tid + NTH * k;
@@ -1942,11 +2046,31 @@ __global__ __launch_bounds__(64) void tail_sse_finalize_kernel(const float* part
   sse[i] = s;
 }
 
+// step_mode 5's second launch: thread (img, k) folds the image's bpi block partials part[block][4] in block order in
+// fp64 (k = 0, 1: sums; 2: min; 3: max) into row *tsel of trace[rows][stride][4]. It runs before the step counter's
+// decrement, so the row is the one the tail just ran; a row outside the buffer is not written.
+__global__ __launch_bounds__(64) void tail_mom_finalize_kernel(const float* part, int bpi, int n, const int* tsel,
+                                                               double* trace, int rows, int stride) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= 4 * n) return;
+  const int row = *tsel;
+  if (row < 0 || row >= rows) return;
+  const int img = i >> 2, k = i & 3;
+  const float* p = part + (size_t)img * bpi * 4 + k;
+  double v = (double)p[0];
+  for (int b = 1; b < bpi; ++b) {
+    const double w = (double)p[4 * b];
+    v = k < 2 ? v + w : k == 2 ? fmin(v, w) : fmax(v, w);
+  }
+  trace[((size_t)row * stride + img) * 4 + k] = v;
+}
+
 // step_mode 2 needs its operands (and nothing of the step's); step_mode 3 its tables and the step's run state;
-// step_mode 4 its two outputs
+// step_mode 4 its two outputs; step_mode 5 what 3 needs and a trace that holds the batch
 static bool tail_x0_ok(const TailArgs& a) {
   if (a.step_mode == 4) return a.vpart && a.vsse;
-  if (a.step_mode == 3) {
+  if (a.step_mode == 5 && !(a.tpart && a.trace && a.trace_rows >= 1 && a.trace_stride >= a.n)) return false;
+  if (a.step_mode == 3 || a.step_mode == 5) {
     for (const float* p : a.xrow)
       if (!p) return false;
     return a.x && a.tsel && a.run && a.nan_flag && (a.clip_x0 == 0 || a.clip_x0 == 1);
@@ -1955,15 +2079,17 @@ static bool tail_x0_ok(const TailArgs& a) {
 }
 
 // The body of a tail launcher from its launch geometry on: launches the instantiation a.step_mode selects (X0K for the
-// x0 epilogue, XSK for the x0-form step, SSEK for the denoising-error sums, PLAIN for eps and step; each under its own
-// name, which the census and the profiles key on) and returns the launch's status. BIG: the four may use up to
-// kTailSmemMax of dynamic shared memory; the attribute is set once. SSEK is followed by its finalize launch, and is
-// refused where a block would straddle two images (the grid is not a whole number of blocks an image).
-#define ITSD_RETURN_TAIL_LAUNCH(PLAIN, X0K, XSK, SSEK, BIG, grid, block, sm, s, a)                             \
+// x0 epilogue, XSK for the x0-form step, SSEK for the denoising-error sums, MOMK for the x0-form step with moments,
+// PLAIN for eps and step; each under its own name, which the census and the profiles key on) and returns the launch's
+// status. BIG: the five may use up to kTailSmemMax of dynamic shared memory; the attribute is set once. SSEK and MOMK
+// are followed by their finalize launches, and are refused where a block would straddle two images (the grid is not a
+// whole number of blocks an image).
+#define ITSD_RETURN_TAIL_LAUNCH(PLAIN, X0K, XSK, SSEK, MOMK, BIG, grid, block, sm, s, a)                       \
   do {                                                                                                         \
     static bool attr = !(BIG);                                                                                 \
     if (!attr) {                                                                                               \
-      for (const void* f : {(const void*)PLAIN, (const void*)X0K, (const void*)XSK, (const void*)SSEK}) {      \
+      for (const void* f : {(const void*)PLAIN, (const void*)X0K, (const void*)XSK, (const void*)SSEK,         \
+                            (const void*)MOMK}) {                                                              \
         hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTailSmemMax);  \
         if (e != hipSuccess) return e;                                                                         \
       }                                                                                                        \
@@ -1974,6 +2100,13 @@ static bool tail_x0_ok(const TailArgs& a) {
       ITSD_LAUNCH(SSEK, grid, block, sm, s, a);                                                                \
       ITSD_LAUNCH(tail_sse_finalize_kernel, dim3((2 * (a).n + 63) / 64), dim3(64), 0, s, (a).vpart,            \
                   (int)((grid).x / (a).n), 2 * (a).n, (a).vsse);                                               \
+      return hipGetLastError();                                                                                \
+    }                                                                                                          \
+    if ((a).step_mode == 5) {                                                                                  \
+      if ((a).n < 1 || (grid).x % (a).n) return hipErrorInvalidValue;                                          \
+      ITSD_LAUNCH(MOMK, grid, block, sm, s, a);                                                                \
+      ITSD_LAUNCH(tail_mom_finalize_kernel, dim3((4 * (a).n + 63) / 64), dim3(64), 0, s, (a).tpart,            \
+                  (int)((grid).x / (a).n), (a).n, (a).tsel, (a).trace, (a).trace_rows, (a).trace_stride);      \
       return hipGetLastError();                                                                                \
     }                                                                                                          \
     if ((a).step_mode == 2) ITSD_LAUNCH(X0K, grid, block, sm, s, a);                                           \
@@ -1987,7 +2120,8 @@ hipError_t launch_tail_mfma(const TailArgs& a, hipStream_t s) {
   const dim3 grid(a.n * (a.H / (128 / a.W)));
   const size_t sm = tail_mfma_smem_px(128, a.H, a.W, a.C);
   ITSD_RETURN_TAIL_LAUNCH((tail_mfma_kernel<128, 512>), (tail_mfma_kernel<128, 512, 1>), (tail_mfma_kernel<128, 512, 2>),
-                          (tail_mfma_kernel<128, 512, 3>), true, grid, dim3(512), sm, s, a);
+                          (tail_mfma_kernel<128, 512, 3>), (tail_mfma_kernel<128, 512, 4>), true, grid, dim3(512), sm, s,
+                          a);
 }
 
 template <typename T>
@@ -1997,14 +2131,21 @@ hipError_t launch_tail(const TailArgs& a, hipStream_t s) {
     const size_t sm = 27 * a.C * 4 + (size_t)(64 / a.W + 2) * (a.W + 2) * (a.C * sizeof(T) + 16) + 2 * 4 * 64 * 3 * 4;
     if (sm > kTailSmemMax) return hipErrorInvalidValue;
     const dim3 grid(a.n * (a.H / (64 / a.W)));
-    ITSD_RETURN_TAIL_LAUNCH(tail2_kernel<T>, (tail2_kernel<T, 1>), (tail2_kernel<T, 2>), (tail2_kernel<T, 3>), true, grid,
-                            dim3(256), sm, s, a);
+    ITSD_RETURN_TAIL_LAUNCH(tail2_kernel<T>, (tail2_kernel<T, 1>), (tail2_kernel<T, 2>), (tail2_kernel<T, 3>),
+                            (tail2_kernel<T, 4>), true, grid, dim3(256), sm, s, a);
   }
   const long long total = (long long)a.n * a.H * a.W;
   const dim3 grid((unsigned)((total + 255) / 256));
-  if (a.step_mode == 4 && (a.H * a.W) % 256) return hipErrorInvalidValue;  // (a block of 256 pixels would straddle)
-  ITSD_RETURN_TAIL_LAUNCH(tail_kernel<T>, (tail_kernel<T, 1>), (tail_kernel<T, 2>), (tail_kernel<T, 3>), false, grid,
-                          dim3(256), 27 * a.C * sizeof(float), s, a);
+  if ((a.step_mode == 4 || a.step_mode == 5) && (a.H * a.W) % 256)
+    return hipErrorInvalidValue;  // (a block of 256 pixels would straddle)
+  ITSD_RETURN_TAIL_LAUNCH(tail_kernel<T>, (tail_kernel<T, 1>), (tail_kernel<T, 2>), (tail_kernel<T, 3>),
+                          (tail_kernel<T, 4>), false, grid, dim3(256), 27 * a.C * sizeof(float), s, a);
+}
+// Whether the per-block sums of step_mode 4 / 5 are refused at this geometry: launch_tail (not the MFMA tail, whose
+// blocks are whole rows of one image) falls to tail_kernel and its 256-pixel blocks would straddle two images.
+bool tail_block_straddles(int H, int W, int C) {
+  const bool tiled = W <= 64 && 64 % W == 0 && H % (64 / W) == 0 && C % 32 == 0;
+  return !tiled && (H * W) % 256 != 0;
 }
 template hipError_t launch_tail<float>(const TailArgs&, hipStream_t);
 template hipError_t launch_tail<bf16_t>(const TailArgs&, hipStream_t);

@@ -114,11 +114,29 @@ class GaussianDiffusionSampler:
             eps = (1.0 + self.w) * e - self.w * ne
         return self.predict_xt_prev_mean_from_eps(x_t, t, eps), var
 
+    def new_trace(self, n: int) -> torch.Tensor:
+        """A score trace for runs of up to n images: a NaN-filled fp64 device tensor [n_steps, n, 4]. Passed to
+        ``run(.., trace=)``, row k receives (sum, sum of squares, min, max) of the x_0 estimate step k used for each
+        image (``itsd_sampler_set_trace``); rows not run keep their NaN. It carries ``per_image`` = 3 H W, the D of
+        ``verifier.moment_scores``. ddim only: the ancestral step never forms x_0."""
+        if self.sampler != "ddim":
+            raise ValueError("a score trace needs sampler='ddim': the ancestral step has no x_0 rows (ddim with "
+                             "steps=T, eta=1 is its x0-form equivalent)")
+        if int(n) < 1:
+            raise ValueError(f"a trace holds n >= 1 images, not {n}")
+        t = torch.full((self.n_steps, int(n), 4), float("nan"), dtype=torch.float64, device=self.model.device)
+        size = int(self.model.arch.img_size)
+        t.per_image = 3 * size * size
+        return t
+
     def run(self, x: torch.Tensor, t_begin: Optional[int] = None, t_end: int = 0, labels=None, seed=None,
             noise: Optional[torch.Tensor] = None, noise_offset: int = 0, graph: bool = True, clip=None,
-            sync: bool = True) -> torch.Tensor:
+            sync: bool = True, trace: Optional[torch.Tensor] = None) -> torch.Tensor:
         """In-place steps t_begin..t_end on a contiguous fp32 device tensor x (rows of the schedule: timesteps for
-        ddpm)."""
+        ddpm). ``trace`` (``new_trace``; ddim only) is attached for this call and detached after it: x is the untraced
+        run's bit for bit, and trace[k, :len(x)] holds the x_0 moments of every row k run."""
+        if trace is not None and self.sampler != "ddim":
+            raise ValueError("run(trace=) needs sampler='ddim': the ancestral step has no x_0 rows")
         t_begin = self.n_steps - 1 if t_begin is None else int(t_begin)
         if clip is None:
             clip = t_end == 0
@@ -132,8 +150,16 @@ class GaussianDiffusionSampler:
         if labels is not None:
             labels = labels.flatten().to(x.device, torch.int32).contiguous()
         nat = self._native(x.shape[0])
-        nat.run(x, t_begin, t_end, seed or 0, noise=noise, labels=labels, noise_offset=noise_offset, graph=graph,
-                clip=clip, sync=sync)
+        if trace is None:
+            nat.run(x, t_begin, t_end, seed or 0, noise=noise, labels=labels, noise_offset=noise_offset, graph=graph,
+                    clip=clip, sync=sync)
+            return x
+        nat.set_trace(trace)
+        try:
+            nat.run(x, t_begin, t_end, seed or 0, noise=noise, labels=labels, noise_offset=noise_offset, graph=graph,
+                    clip=clip, sync=sync)
+        finally:  # (host state: steps already queued keep the pointer their launches were given)
+            nat.set_trace(None)
         return x
 
     def predict_x0(self, x: torch.Tensor, t: int, labels: Optional[torch.Tensor] = None) -> torch.Tensor:

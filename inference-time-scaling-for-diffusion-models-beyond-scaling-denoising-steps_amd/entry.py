@@ -22,7 +22,7 @@ Keys beyond the reference (all optional):
   run batched (and sharded over ranks when launched with torchrun) by ``itsd.search.SearchEngine``::
 
       search:
-        algorithm: random        # random | zero_order | path | gradient | none
+        algorithm: random        # random | zero_order | path | gradient | particle | none
         n_candidates: 256        # random
         n_neighbors: 4           # zero_order
         lambda_radius: 0.95
@@ -34,6 +34,10 @@ Keys beyond the reference (all optional):
         sigma: 0.05              # gradient: the perturbation radius of the ES estimate
         lr: 0.01                 # gradient: Adam's learning rate (n_iterations defaults to 20 here)
         shaping: raw             # gradient: raw | rank (scores, or their centred ranks)
+        n_particles: 4           # particle
+        resample_steps: [6, 3]   # particle: rows of the ddim sampler (an int, or a strictly decreasing list)
+        lam: 1.0                 # particle: the weights are exp(lam x potential)
+        potential: diff          # particle: diff | max
         verifier: oracle         # oracle | selfsup | aesthetic | denoise | class
         verifier_probes: 4       # denoise / class: UNet evaluations an image (rows spread over the sampler's
                                  # schedule), or an explicit list of rows
@@ -43,6 +47,12 @@ Keys beyond the reference (all optional):
   ``gradient`` is ``GradientBasedSearch`` without autograd (``SearchEngine.gradient_search``):
   an evolution-strategies estimate of the score's gradient from antithetic candidates, stepped by Adam; it is
   label-aware like ``zero_order`` and pairs best with a deterministic sampler (``sampler: {kind: ddim, eta: 0}``).
+
+  ``particle`` is particle resampling along the trajectory (``SearchEngine.fk_search``): the
+  few-step sampler leaves every step's x_0 moments in a score trace, and at each resample row the particles are
+  resampled in proportion to exp(lam x potential) of the trace's scores, at no extra UNet evaluation. It reads
+  ``n_particles``, ``noise_scale``, ``resample_steps``, ``lam`` and ``potential``, needs ``sampler: {kind: ddim}`` with
+  ``eta > 0`` and a ``verifier`` of oracle | aesthetic; every bad value raises a ValueError naming its key.
 
   ``denoise`` and ``class`` score with the diffusion model itself (``itsd.verifier.DenoisingVerifier``, no reference
   counterpart: the reference's content-aware verifiers need downloaded CLIP / DINO weights): the squared error of the
@@ -474,6 +484,51 @@ def search_verifier(s: Dict[str, Any], sampler, has_labels: bool):
         raise ValueError(f"search.verifier {vname} / search.verifier_probes: {e}") from e
 
 
+def particle_args(cfg: Dict[str, Any], T: int) -> Dict[str, Any]:
+    """``search.algorithm: particle``'s keys as ``SearchEngine.fk_search``'s arguments. Every bad value raises a
+    ValueError naming its key; a ``sampler`` block that is not ddim with eta > 0 is one of them (copies of a parent
+    diverge only through the step noise). T: the inference T the ``sampler`` block strides over."""
+    import numbers
+
+    s = cfg.get("search") or {}
+    kw = sampler_kwargs(cfg, T)
+    if kw.get("sampler") != "ddim" or not kw["eta"] > 0:
+        raise ValueError("sampler.kind / sampler.eta: search.algorithm particle needs kind: ddim and eta > 0 (the score trace is the "
+                         "x0-form step's, and copies of a parent diverge only through the step noise)")
+    rows = int(T if kw["steps"] is None else kw["steps"])
+
+    def integer(v):
+        return isinstance(v, numbers.Integral) and not isinstance(v, bool)
+
+    def number(v):
+        return isinstance(v, numbers.Real) and not isinstance(v, bool) and v == v and abs(v) != float("inf")
+
+    n = s.get("n_particles", 4)
+    if not integer(n) or n < 1:
+        raise ValueError(f"search.n_particles = {n!r} must be an integer >= 1")
+    scale = s.get("noise_scale", 0.1)
+    if not number(scale) or scale < 0:
+        raise ValueError(f"search.noise_scale = {scale!r} must be a number >= 0")
+    rs = s.get("resample_steps")
+    steps = list(rs) if isinstance(rs, (list, tuple)) else [rs]
+    if (not steps or not all(integer(v) for v in steps) or any(b >= a for a, b in zip(steps, steps[1:]))
+            or steps[-1] < 1 or steps[0] > rows - 2):
+        raise ValueError(f"search.resample_steps = {rs!r} must be an integer or a strictly decreasing list of rows "
+                         f"in [1, sampler rows - 2 = {rows - 2}]")
+    lam = s.get("lam", 1.0)
+    if not number(lam):
+        raise ValueError(f"search.lam = {lam!r} must be a finite number")
+    pot = s.get("potential", "diff")
+    if pot not in ("diff", "max"):
+        raise ValueError(f"search.potential = {pot!r} must be diff or max")
+    vname = (s.get("verifier") or "oracle").lower()
+    if vname not in ("oracle", "aesthetic"):
+        raise ValueError(f"search.verifier {vname} has no moment form: search.algorithm particle scores from the "
+                         "sampler's x_0 moments (oracle | aesthetic)")
+    return {"n_particles": int(n), "noise_scale": float(scale), "resample_steps": [int(v) for v in steps],
+            "lam": float(lam), "potential": pot}
+
+
 def _search(cfg: Dict[str, Any], sampler, img_size: int, labels: Optional[torch.Tensor]) -> Optional[Dict[str, Any]]:
     s = cfg.get("search") or {}
     algo = (s.get("algorithm") or "none").lower()
@@ -481,6 +536,8 @@ def _search(cfg: Dict[str, Any], sampler, img_size: int, labels: Optional[torch.
         return None
     from .search import SearchEngine
 
+    if algo == "particle":  # (its keys are checked before any verifier or engine is built)
+        pk = particle_args(cfg, int(sampler.T))
     vname = (s.get("verifier") or "oracle").lower()
     ver = search_verifier(s, sampler, labels is not None)
     shape = (int(s.get("batch_per_candidate") or 1), 3, img_size, img_size)
@@ -505,6 +562,8 @@ def _search(cfg: Dict[str, Any], sampler, img_size: int, labels: Optional[torch.
             best, score, hist = eng.gradient_search(init, int(s.get("n_pairs") or 4), float(s.get("sigma", 0.05)),
                                                     20 if n_it is None else int(n_it), lr=float(s.get("lr", 0.01)),
                                                     shaping=str(s.get("shaping") or "raw").lower(), labels=lab)
+        elif algo == "particle":
+            best, score, hist = eng.fk_search(init, labels=lab, **pk)
         elif algo == "path":
             mode = (s.get("path_mode") or "placeholder").lower()
             n_paths, inj = int(s.get("n_paths") or 4), s.get("injection_step") or 400

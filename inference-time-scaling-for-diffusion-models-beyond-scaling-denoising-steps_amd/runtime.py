@@ -96,6 +96,7 @@ _SIGS = {
     "itsd_set_schedule_x0": [ctypes.c_void_p, ctypes.POINTER(X0Schedule)],
     "itsd_sampler_run": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                          ctypes.c_uint64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p],
+    "itsd_sampler_set_trace": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int],
     "itsd_sampler_predict_x0": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                 ctypes.c_float, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p],
     "itsd_verify_denoise": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
@@ -277,6 +278,17 @@ class NativeUNet:
                                      int(seed) & ((1 << 64) - 1), int(noise_offset), _ptr(noise), flags,
                                      stream_ptr(x.device)))
 
+    def set_trace(self, trace: Optional[torch.Tensor]) -> None:
+        """Attach a score trace (``itsd_sampler_set_trace``): a contiguous fp64 device tensor [rows, stride, 4] that
+        every later ``run`` step k fills at [k, :n] with (sum, sum of squares, min, max) of the x0 it used; ``None``
+        detaches. The caller keeps the tensor alive while it is attached."""
+        if trace is None:
+            check(lib().itsd_sampler_set_trace(self.h, None, 0, 0))
+            return
+        assert trace.dtype == torch.float64 and trace.is_cuda and trace.is_contiguous() and trace.dim() == 3 \
+            and trace.shape[2] == 4, "trace is a contiguous fp64 device tensor [rows, stride, 4]"
+        check(lib().itsd_sampler_set_trace(self.h, trace.data_ptr(), int(trace.shape[0]), int(trace.shape[1])))
+
     def predict_x0(self, x: torch.Tensor, t: int, a0: float, b0: float, out: torch.Tensor,
                    labels: Optional[torch.Tensor] = None) -> torch.Tensor:
         """out = clip(a0 x - b0 eps(x, t[, labels]), -1, 1) with the sampler step's own eps; x is only read."""
@@ -308,7 +320,7 @@ class NativeUNet:
         return sse
 
     def query(self, key: str) -> int:
-        """itsd_unet_query: "graph_captures", "max_batch", "T_sched", "sched_form", "ws_bytes", "ops"."""
+        """itsd_unet_query: "graph_captures", "max_batch", "T_sched", "sched_form", "trace", "ws_bytes", "ops"."""
         v = ctypes.c_int64()
         check(lib().itsd_unet_query(self.h, key.encode(), ctypes.byref(v)))
         return int(v.value)

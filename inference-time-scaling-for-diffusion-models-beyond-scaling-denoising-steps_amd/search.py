@@ -44,6 +44,7 @@ _STREAM_INIT = 0xD0000000    # the initial pivot of zero-order / path search
 _STREAM_BRANCH = 0xC0000000  # + stage index: the re-noising draws of a branching path search
 _STREAM_ES = 0xB0000000      # + round id: the pair draws z_p of a gradient search's iteration
 _ROUND_BRANCH = 0x5B000000   # + window index (>= 1): the sampler keys of the windows after a branch
+_ROUND_RESAMPLE = 0x5F000000  # + stage index: the CPU generator seed of a particle search's resampling offset u
 
 
 def strict_argmax(scores: torch.Tensor) -> Tuple[int, float]:
@@ -82,6 +83,70 @@ def root_of(parents: Sequence[Sequence[int]], index: int) -> int:
             break
         index = tab[index]
     return index
+
+
+FK_POTENTIALS = ("diff", "max")
+
+
+def _f64(v) -> torch.Tensor:
+    """v as a flat fp64 CPU tensor (a list of Python floats keeps its fp64 values)."""
+    if isinstance(v, torch.Tensor):
+        return v.detach().double().cpu().flatten()
+    return torch.as_tensor(v, dtype=torch.float64).flatten()
+
+
+def fk_weights(score_now, score_prev, lam: float) -> torch.Tensor:
+    """The Feynman-Kac resampling weights of one stage, exp(lam (now - prev)) per particle, in fp64 on the CPU.
+    A particle whose weight is NaN (a NaN score on either side) gets 0, so it never has children. If any weight
+    overflows to +inf those particles share the stage (1 each, every other 0). If every weight is 0 the weights are
+    uniform: a stage never kills the whole population."""
+    now, prev = _f64(score_now), _f64(score_prev)
+    if prev.numel() == 1:
+        prev = prev.expand_as(now)
+    if now.numel() < 1 or now.shape != prev.shape:
+        raise ValueError("fk_weights needs N >= 1 scores and as many previous scores (or one)")
+    lam = float(lam)
+    if lam != lam or lam in (float("inf"), float("-inf")):
+        raise ValueError("lam must be finite")
+    w = torch.exp(lam * (now - prev))
+    w = torch.where(torch.isnan(w), torch.zeros_like(w), w)
+    if bool(torch.isinf(w).any()):
+        w = torch.isinf(w).double()
+    if not bool((w > 0).any()):
+        w = torch.ones_like(w)
+    return w
+
+
+def systematic_parents(weights, u: float) -> List[int]:
+    """Systematic resampling: N = len(weights) parent indices, non-decreasing, from ONE uniform u in [0, 1). With
+    c_i the cumulative normalised weight, child j takes the first parent i with c_i > (j + u) / N, so parent i gets
+    floor or ceil of N w~_i children. Evaluated as c_i N - j total > u total on weights scaled by their maximum, in
+    fp64: equal weights give the identity table for every u, exactly."""
+    w = _f64(weights).tolist()
+    n, u = len(w), float(u)
+    if n < 1 or any(not (v >= 0.0) or v == float("inf") for v in w) or not max(w) > 0.0:
+        raise ValueError("systematic_parents needs N >= 1 finite weights >= 0, not all 0")
+    if not 0.0 <= u < 1.0:
+        raise ValueError(f"u = {u} outside [0, 1)")
+    top = max(w)
+    cum, acc = [], 0.0
+    for v in w:
+        acc += v / top
+        cum.append(acc)
+    total = cum[-1]
+    out, i = [], 0
+    for j in range(n):
+        while i < n - 1 and not cum[i] * n - j * total > u * total:
+            i += 1
+        out.append(i)
+    return out
+
+
+def resample_u(seed: int, stage: int) -> float:
+    """The stage's resampling offset: one fp64 uniform of a CPU generator seeded by (engine seed, stage), so every
+    rank computes the same parent table."""
+    g = torch.Generator().manual_seed((int(seed) * 1000003 + _ROUND_RESAMPLE + int(stage)) & ((1 << 62) - 1))
+    return float(torch.rand(1, generator=g, dtype=torch.float64).item())
 
 
 ES_SHAPINGS = ("raw", "rank")
@@ -543,6 +608,125 @@ class SearchEngine:
                                              "unet_steps": n_paths * (ran + len(steps))})
 
 
+    # --- particle resampling on the sampler's score trace (Feynman-Kac steering)
+    def fk_search(self, initial_noise: torch.Tensor, n_particles: int, noise_scale: float,
+                  resample_steps: Sequence[int], lam: float, potential: str = "diff", labels=None):
+        """Sequential Monte Carlo over the denoising trajectory. N = n_particles particles start as ``path_search``'s
+        round-0 candidates and are denoised with a score trace attached (``sampler.run(.., trace=)``): every step
+        leaves each particle's x_0 moments, so a particle's score at any row costs no UNet evaluation. At each
+        resample row s (strictly decreasing, 1 <= s <= T - 2; rows of the few-step sampler, T its ``n_steps``) the
+        particles have been denoised down to x_s and are scored by ``moment_scores`` of trace row s + 1, the LAST STEP
+        RUN: the x_0 estimate formed from x_{s+1}, one row staler than ``predict_x0(x_s, s)`` would give. They are then
+        resampled in proportion to ``fk_weights`` of the potential,
+
+        * ``diff``: the score now minus the particle's score at the previous stage (0 at the first stage);
+        * ``max``:  the particle's running maximum over ALL rows run so far minus that maximum at the previous stage
+          (0 at the first stage) -- what needs the dense trace,
+
+        by ``systematic_parents`` with the stage's ``resample_u``. Children inherit their parent's history (previous
+        score, running maximum) and are exact copies (``itsd_branch`` with a = 1, b = 0) that keep the window key:
+        they diverge only through the sampler's per-position step noise, so the sampler must be ddim with eta > 0 and
+        a non-zero sg row. A stage's collectives are ``path_search_branch``'s: one all_gather of the window's trace
+        scores ([rows of the window] x N) and, when world > 1, one of the latents. The finished images are scored by
+        the engine's verifier, as in ``path_search``.
+
+        Returns (best_noise, best_score, hist): best_noise the initial noise of the winner's root ancestor (as
+        ``path_search_branch``: the winning image is ``self.best_image``). hist: ``scores`` (final, N),
+        ``stage_scores`` [m][N], ``weights`` [m][N], ``ess`` [m] (1 / sum w~^2), ``parents`` [m][N],
+        ``trace_scores`` [rows run][N] (row T - 1 first; after a stage a column is the particle then at that index),
+        ``resample_steps``, ``potential``, ``best_index``, ``root_index`` and ``unet_steps`` = N x rows run: no stage
+        costs an evaluation."""
+        from .verifier import moment_scores
+
+        kind = getattr(self.verifier, "trace_kind", None)
+        if kind is None:
+            raise ValueError("fk_search scores particles from the sampler's x_0 moments: the verifier needs a "
+                             "trace_kind (OracleVerifier, AestheticPredictor)")
+        if getattr(self.sampler, "sampler", "ddpm") != "ddim":
+            raise ValueError("fk_search needs sampler='ddim': the ancestral step leaves no score trace")
+        sg = self.sampler.rows["sg"]
+        if float(getattr(self.sampler, "eta", 0.0)) == 0.0 or not bool((torch.as_tensor(sg) != 0).any()):
+            raise ValueError("fk_search needs eta > 0 and a non-zero sg row: copies of a parent diverge only through "
+                             "the per-step noise")
+        if self.noise == "reference":
+            raise ValueError("the particle search draws from Philox; noise='reference' covers the placeholder")
+        if potential not in FK_POTENTIALS:
+            raise ValueError(f"potential must be one of {FK_POTENTIALS}")
+        T = int(self.sampler.n_steps)
+        if isinstance(resample_steps, (list, tuple)) and resample_steps and all(int(s) == s for s in resample_steps):
+            steps = [int(s) for s in resample_steps]
+        else:
+            raise ValueError("resample_steps must be a non-empty list of ints")
+        if any(b >= a for a, b in zip(steps, steps[1:])):
+            raise ValueError(f"resample_steps {steps} must be strictly decreasing")
+        if steps[-1] < 1 or steps[0] > T - 2:
+            raise ValueError(f"every resample step s needs 1 <= s <= T - 2 = {T - 2}")
+        n, lam = int(n_particles), float(lam)
+        fk_weights([0.0], [0.0], lam)  # (refuses a non-finite lam before any work)
+        shape = tuple(initial_noise.shape)
+        self._begin_search()
+        self.reserve(n, shape)
+        g0, nl = self.shard(n)
+        b, per = int(shape[0]), int(torch.Size(shape).numel())
+        lab = None if labels is None else labels.to(self.device).flatten().repeat(nl)
+        pivot = initial_noise.to(self.device, torch.float32).contiguous()
+        x = self.candidate_noise(0, g0, nl, shape, pivot, noise_scale)  # round 0: the placeholder's candidates
+        trace = self.sampler.new_trace(nl * b)
+        per_image = int(torch.Size(shape[1:]).numel())
+
+        def window(i: int, t_hi: int, t_lo: int, clip: bool) -> torch.Tensor:
+            """Rows t_hi .. t_lo under window i's key, traced; returns their scores [t_hi - t_lo + 1][N] (CPU)."""
+            self.sampler.run(x, t_begin=t_hi, t_end=t_lo, labels=lab, seed=self.window_key(i, 0),
+                             noise_offset=g0 * per, graph=self.graph, clip=clip, trace=trace)
+            rows = trace[t_lo:t_hi + 1, :nl * b].flip(0)
+            local = moment_scores(rows, kind, b, per_image).t().contiguous()  # [nl][rows]: gathers along particles
+            return ((self._gather(local) if self.dist else local).t()).cpu()
+
+        prev = torch.zeros(n, dtype=torch.float64)
+        run_max = torch.full((n,), float("-inf"), dtype=torch.float64)
+        prev_max = torch.zeros(n, dtype=torch.float64)
+        t_hi = T - 1
+        stage_scores, weights, ess, parents, trace_scores = [], [], [], [], []
+        for i, s in enumerate(steps):
+            win = window(i, t_hi, s + 1, False)                # first collective of the stage
+            src = self._gather(x) if self.world > 1 else x     # second: every rank holds all N latents
+            trace_scores += win.tolist()
+            now = win[-1]
+            run_max = torch.fmax(run_max, torch.where(torch.isnan(win), torch.full_like(win, float("-inf")),
+                                                      win).amax(dim=0))
+            if potential == "diff":
+                w = fk_weights(now, prev, lam)
+            else:
+                seen = torch.where(torch.isinf(run_max), torch.full_like(run_max, float("nan")), run_max)
+                w = fk_weights(seen, prev_max, lam)
+            tab = systematic_parents(w, resample_u(self.seed, i))
+            wn = w / w.sum()
+            x = self.branch_latents(torch.empty_like(x), src, tab[g0:g0 + nl], 1.0, 0.0, i, g0)
+            idx = torch.tensor(tab, dtype=torch.long)
+            prev, run_max = now[idx], run_max[idx]
+            prev_max = torch.where(torch.isinf(run_max), torch.zeros_like(run_max), run_max)
+            stage_scores.append(now.tolist())
+            weights.append(w.tolist())
+            ess.append(float(1.0 / (wn * wn).sum()))
+            parents.append(tab)
+            t_hi = s
+        trace_scores += window(len(steps), t_hi, 0, True).tolist()
+        local = self._score(x, nl, lab)
+        self.nfes += n
+        sc = (self._gather(local) if self.dist else local).cpu()
+        best_index, best_score = strict_argmax(sc)
+        root = root_of(parents, best_index)
+        best = pivot.clone()  # (kept when no particle beats -inf, as the placeholder)
+        if best_index >= 0:
+            best = self.candidate_noise(0, root, 1, shape, pivot=pivot, scale=noise_scale)
+            self._keep_best_image(RoundResult(sc, best_index, best_score, x, g0), shape)
+        self._publish_best_image(shape)
+        return best, best_score, self._hist({"scores": sc.tolist(), "stage_scores": stage_scores, "weights": weights,
+                                             "ess": ess, "parents": parents, "trace_scores": trace_scores,
+                                             "resample_steps": steps, "potential": potential,
+                                             "best_index": best_index, "root_index": root, "unet_steps": n * T})
+
+
 # --------------------------------------------------------------------------- reference API
 def injection_step_list(injection_step) -> List[int]:
     """``injection_step`` as the list a branching search takes: an int is one stage."""
@@ -703,6 +887,39 @@ class PathSearch:
             if s > best_score:
                 best_score, best_noise = s, pert.clone()
         return best_noise, best_score, history
+
+    def reset_nfes(self):
+        self.nfes = 0
+
+
+class ParticleSearch:
+    """Particle resampling along the denoising trajectory (no reference counterpart; ``SearchEngine.fk_search``).
+    Batched searches only: an opaque ``denoise_fn`` can neither be stopped mid-trajectory nor leave a score trace.
+    ``sampler`` must be a ddim sampler with eta > 0 and ``verifier_fn`` an image-statistics verifier (one with a
+    ``trace_kind``)."""
+
+    def __init__(self, n_particles: int = 4, resample_steps=1, noise_scale: float = 0.1, lam: float = 1.0,
+                 potential: str = "diff", verbose: bool = False):
+        if potential not in FK_POTENTIALS:
+            raise ValueError(f"potential must be one of {FK_POTENTIALS}")
+        self.n_particles = n_particles
+        self.resample_steps = resample_steps
+        self.noise_scale = noise_scale
+        self.lam = lam
+        self.potential = potential
+        self.verbose = verbose
+        self.nfes = 0
+
+    def search(self, initial_noise: torch.Tensor, denoise_fn: Callable, verifier_fn: Callable, device: str = "cuda",
+               batched: bool = False, sampler=None, seed: int = 0, **kwargs):
+        if not batched:
+            raise ValueError("ParticleSearch needs batched=True: an opaque denoise_fn cannot be stopped "
+                             "mid-trajectory and leaves no score trace")
+        eng = _engine(sampler, verifier_fn, seed, False)
+        out = eng.fk_search(initial_noise, self.n_particles, self.noise_scale,
+                            injection_step_list(self.resample_steps), self.lam, self.potential)
+        self.nfes += self.n_particles
+        return out
 
     def reset_nfes(self):
         self.nfes = 0

@@ -37,6 +37,7 @@ class OracleVerifier(_NativeVerifier):
     """``verifier.py:30-66``: 1/(1 + mean_b var(x_b)) when no dataset stats are given."""
 
     kind = rt.VERIFY_ORACLE
+    trace_kind = "oracle"  # its score is a function of a sampler trace's moments (moment_scores)
 
     def __init__(self, dataset_stats: Optional[Dict[str, np.ndarray]] = None):
         self.dataset_stats = dataset_stats
@@ -75,6 +76,7 @@ class AestheticPredictor(_NativeVerifier):
     """``verifier.py:251-287``: (x+1)/2 if the candidate has negatives, then 2 * mean std."""
 
     kind = rt.VERIFY_AESTHETIC
+    trace_kind = "aesthetic"
 
     def __init__(self, device: str = "cuda"):
         self.device = device
@@ -82,6 +84,41 @@ class AestheticPredictor(_NativeVerifier):
 
     def score(self, images: torch.Tensor) -> float:
         return float(self.score_batch(images, 1)[0].item())
+
+
+MOMENT_KINDS = ("oracle", "aesthetic")
+
+
+def moment_scores(moments: torch.Tensor, kind: str, b: int = 1, per_image: Optional[int] = None) -> torch.Tensor:
+    """The image-statistics verifiers from per-image moments instead of pixels, in fp64. ``moments``:
+    [..., n_cand * b, 4] = (S = sum x, Q = sum x^2, min, max) of each image over its D elements -- a row (or all rows)
+    of a sampler trace; returns [..., n_cand]. D is ``per_image``, or the ``per_image`` attribute a trace from
+    ``GaussianDiffusionSampler.new_trace`` carries. Per image var = (Q - S^2 / D) / (D - 1) (torch.var's unbiased
+    form), clamped at 0 against cancellation.
+
+    * ``oracle``:    1 / (1 + mean_b var)                                  (``OracleVerifier``)
+    * ``aesthetic``: 2 mean_b std, the std halved when the candidate's min over its b images is < 0 -- the
+      (x + 1) / 2 shift of ``AestheticPredictor`` shifts the mean away and halves the spread.
+
+    ``selfsup`` (pooled features), ``denoise`` and ``class`` (model evaluations) are no functions of these moments."""
+    if kind not in MOMENT_KINDS:
+        raise ValueError(f"verifier kind {kind!r} has no moment form: only {MOMENT_KINDS} are functions of an image's "
+                         "sum, sum of squares and min (selfsup needs pooled features, denoise / class the model)")
+    D = per_image if per_image is not None else getattr(moments, "per_image", None)
+    if D is None or int(D) < 2:
+        raise ValueError("moment_scores needs per_image = 3 H W (>= 2), passed in or carried by the trace")
+    D, b = float(int(D)), int(b)
+    m = torch.as_tensor(moments).double()
+    if m.shape[-1] != 4 or b < 1 or m.shape[-2] % b:
+        raise ValueError(f"moments must be [..., n_cand * b, 4] with b = {b}, not {tuple(m.shape)}")
+    m = m.reshape(m.shape[:-2] + (m.shape[-2] // b, b, 4))
+    S, Q, lo = m[..., 0], m[..., 1], m[..., 2]
+    var = ((Q - S * S / D) / (D - 1.0)).clamp_min(0.0)
+    if kind == "oracle":
+        return 1.0 / (1.0 + var.mean(dim=-1))
+    std = var.sqrt()
+    shifted = lo.amin(dim=-1, keepdim=True) < 0
+    return 2.0 * torch.where(shifted, 0.5 * std, std).mean(dim=-1)
 
 
 _STREAM_PROBE = 0xD0000000  # + probe index: the Philox stream id of a probe's noise field

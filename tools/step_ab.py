@@ -5,6 +5,10 @@ process, interleaved. Measurement tool, never part of the product.
 
 --samplers ddpm,ddim times the ancestral step and the x0-form step (every timestep a row, so both run the same UNet
 evaluations; --eta, --clip-x0) side by side, interleaved like the variants.
+
+--trace times the x0-form step with a score trace attached (the "x0 step + moments" tail and its finalize launch)
+against the same build's untraced x0-form step, alternating in one process: arms untraced, traced, untraced again --
+the second untraced arm is the A/A spread the difference is read against.
 """
 import argparse
 import os
@@ -28,6 +32,33 @@ DEFAULTS = {"gn_fold": 1, "p5": 1, "p5_split": 0, "p5_sc": 1, "splitk_inl": 1, "
             "attn_fuse": 1, "fuse_gn": 1, "conv_dbg": 0, "p4_xcd": 2, "spin_bound": 1 << 22, "p4_c96": 1, "p5_dist": 1, "p5_pub": 1, "small_gn": 1, "p5_xl": 3}
 
 
+def trace_ab(args, smp, x, run_kw):
+    """--trace: ms/step of the arms (untraced, traced, untraced again), alternating, args.rounds times."""
+    trace = smp.new_trace(args.n)
+    arms = [("untraced", None), ("traced", trace), ("untraced_again", None)]
+    res = {k: [] for k, _ in arms}
+    for r in range(args.rounds):
+        for name, tr in arms:
+            smp.run(x.clone(), t_begin=999, t_end=999 - 4, seed=1, trace=tr, **run_kw)  # capture + warm
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            smp.run(x.clone(), t_begin=999, t_end=999 - args.steps + 1, seed=1, trace=tr, **run_kw)
+            torch.cuda.synchronize()
+            ms = (time.perf_counter() - t0) * 1e3 / args.steps
+            res[name].append(ms)
+            print(f"round {r} {name}: {ms:.4f} ms/step", flush=True)
+    assert bool(torch.isfinite(trace[999 - args.steps + 1:]).all()), "the traced arm left rows unwritten"
+    best = {k: min(v) for k, v in res.items()}
+    med = {k: sorted(v)[len(v) // 2] for k, v in res.items()}
+    for k in res:
+        print(f"{k}: best {best[k]:.4f} median {med[k]:.4f} ms/step")
+    base = min(best["untraced"], best["untraced_again"])
+    print(f"traced - untraced (best of each): {(best['traced'] - base) * 1e3:+.1f} us/step "
+          f"({(best['traced'] / base - 1) * 100:+.3f} %); A/A spread of the two untraced arms: "
+          f"{abs(best['untraced'] - best['untraced_again']) * 1e3:.1f} us/step "
+          f"({abs(best['untraced'] / best['untraced_again'] - 1) * 100:.3f} %)")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=32)
@@ -41,7 +72,10 @@ def main():
     ap.add_argument("--samplers", default="ddpm", help="ddpm (the ancestral step), ddim (the x0-form step), or both: ddpm,ddim")
     ap.add_argument("--eta", type=float, default=1.0, help="ddim: eta (0: no draw at all)")
     ap.add_argument("--clip-x0", type=int, default=1, help="ddim: clip the x_0 estimate (0 | 1)")
+    ap.add_argument("--trace", action="store_true", help="the traced against the untraced ddim step (and an A/A arm)")
     args = ap.parse_args()
+    if args.trace:
+        args.samplers, args.variants = "ddim", "base"
     if args.lib:
         rt.LIB_PATH = os.path.abspath(args.lib)
     for kv in filter(None, args.create_set.split("+")):
@@ -67,6 +101,9 @@ def main():
             for k in kinds}
     x = torch.randn(args.n, 3, args.img, args.img, device="cuda")
     variants = [v if len(kinds) == 1 else f"{v}/{k}" for v in args.variants.split(",") for k in kinds]
+    if args.trace:
+        trace_ab(args, smps["ddim"], x, run_kw)
+        return
     res = {v: [] for v in variants}
     for r in range(args.rounds):
         for v in variants:
