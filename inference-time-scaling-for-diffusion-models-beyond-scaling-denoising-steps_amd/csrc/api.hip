@@ -1370,7 +1370,7 @@ RunCtx forward_ctx(const itsd_unet* u, int n, const float* x, const int32_t* lab
   c.nb = n; c.x = x; c.x_mod = n;
   c.temb = u->proj_buf; c.tsel = nullptr; c.temb_img_stride = u->sumC;
   c.labels = labels; c.label_mod = n; c.uncond_from = -1;
-  c.tail.n = n; c.tail.cfg = 0; c.tail.step_mode = 0; c.tail.eps_out = eps_out;
+  c.tail.n = n; c.tail.cfg = 0; c.tail.step_mode = kTailEps; c.tail.eps_out = eps_out;
   return c;
 }
 
@@ -1829,13 +1829,13 @@ int itsd_sampler_run(itsd_unet* u, float* x, const int32_t* labels, int n, int t
 
   RunCtx c = step_ctx(u, n, u->x_state, labels ? u->lab_state : nullptr);
   TailArgs& t = c.tail;
-  t.step_mode = u->sched_form ? 3 : 1; t.tsel = u->d_t;
+  t.step_mode = u->sched_form ? kTailX0Step : kTailStep; t.tsel = u->d_t;
   t.coeff1 = u->coeff1; t.coeff2 = u->coeff2; t.sqrt_var = u->sqrt_var;
   if (u->sched_form) {  // rows, not timesteps: d_t, the Philox stream id and the injected-noise index are the row
     for (int i = 0; i < 5; ++i) t.xrow[i] = u->xrow + (size_t)i * u->T_sched;
     t.clip_x0 = u->clip_x0;
     if (u->trace) {
-      t.step_mode = 5;
+      t.step_mode = kTailX0StepMom;
       t.tpart = u->tr_part; t.trace = u->trace; t.trace_rows = u->trace_rows; t.trace_stride = u->trace_stride;
     }
   }
@@ -1894,7 +1894,7 @@ int itsd_sampler_set_trace(itsd_unet* u, double* trace, int rows, int stride) {
 }
 
 // The x_0 estimate of the state x at step t: the sampler step's own program (the doubled cond||uncond batch for CFG,
-// the time-embedding row selected on the device through d_t) with the tail's x0 epilogue (TailArgs::step_mode 2).
+// the time-embedding row selected on the device through d_t) with the tail's x0 epilogue (TailArgs::step_mode kTailX0).
 // Eager, on x itself: no step graph is captured, looked up or evicted, and the sampler's run parameters and NaN flag
 // stay as the last run left them.
 int itsd_sampler_predict_x0(itsd_unet* u, const float* x, const int32_t* labels, int n, int t, float a0, float b0,
@@ -1910,7 +1910,7 @@ int itsd_sampler_predict_x0(itsd_unet* u, const float* x, const int32_t* labels,
   CHK(enter_stream(u, cs));
   u->last_forward_n = 0;  // (the tail input is overwritten: itsd_unet_representation refuses until the next forward)
   RunCtx c = step_ctx(u, n, const_cast<float*>(x), labels);
-  c.tail.step_mode = 2; c.tail.a0 = a0; c.tail.b0 = b0; c.tail.x0_out = x0;
+  c.tail.step_mode = kTailX0; c.tail.a0 = a0; c.tail.b0 = b0; c.tail.x0_out = x0;
   HIPCHK(launch_set_int(u->d_t, t, s));
   HIPCHK(hipMemsetAsync(u->d_nan + 1, 0, 4, s));  // this forward's hand-off status (itsd_unet_query "status")
   CHK(run_program(u, c, resolve_program(u, c), s));
@@ -1919,7 +1919,7 @@ int itsd_sampler_predict_x0(itsd_unet* u, const float* x, const int32_t* labels,
 
 // One denoising-error probe: x0 noised to row t with the probe's own noise field (probe_noise_kernel, into the handle's
 // scratch), then the sampler step's program on it -- as itsd_sampler_predict_x0: the doubled cond||uncond batch for
-// CFG, the time-embedding row selected on the device -- with the tail's sse epilogue (TailArgs::step_mode 4), which
+// CFG, the time-embedding row selected on the device -- with the tail's sse epilogue (TailArgs::step_mode kTailSse), which
 // re-draws the same field and leaves sse[n][2]. Eager: no step graph is captured, looked up or evicted, and the
 // sampler's run parameters and NaN flag stay as the last run left them.
 int itsd_verify_denoise(itsd_unet* u, const float* x0, const int32_t* labels, int n, int t, float a, float b,
@@ -1943,7 +1943,7 @@ int itsd_verify_denoise(itsd_unet* u, const float* x0, const int32_t* labels, in
   if (xt_out) HIPCHK(hipMemcpyAsync(xt_out, u->vd_xt, (size_t)n * per * 4, hipMemcpyDeviceToDevice, s));
   RunCtx c = step_ctx(u, n, u->vd_xt, labels);
   TailArgs& ta = c.tail;
-  ta.step_mode = 4; ta.noise = noise; ta.vseed = seed; ta.vstream = stream_id;
+  ta.step_mode = kTailSse; ta.noise = noise; ta.vseed = seed; ta.vstream = stream_id;
   ta.vpart = u->vd_part; ta.vsse = sse; ta.eps_out = eps_out;
   HIPCHK(launch_set_int(u->d_t, t, s));
   HIPCHK(hipMemsetAsync(u->d_nan + 1, 0, 4, s));  // this forward's hand-off status (itsd_unet_query "status")

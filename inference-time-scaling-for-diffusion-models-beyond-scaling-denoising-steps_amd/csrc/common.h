@@ -113,6 +113,11 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+__device__ __forceinline__ float wave_min(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
+  return v;
+}
 
 // ----------------------------------------------------------------------------- register-epilogue pieces
 // The MFMA kernels that write bf16 straight from their 32x32 accumulators (conv3x3_gn_p4 / p5_kernel,
@@ -382,6 +387,30 @@ struct RunParams {
   int pad_;
 };
 
+// The six ways the tail ends (TailArgs::step_mode; kernels.hip's header comment describes each). The values are the
+// ABI of TailArgs and stay.
+enum TailMode : int {
+  kTailEps = 0,        // write eps NCHW (the forward API)
+  kTailStep = 1,       // the ancestral update of x in place
+  kTailX0 = 2,         // x0_out = clip(a0 x - b0 eps), x read only
+  kTailX0Step = 3,     // the x0-form update of x in place (rows of xrow)
+  kTailSse = 4,        // the denoising-error sums
+  kTailX0StepMom = 5,  // kTailX0Step plus the x0 moments of every image
+};
+// EPI, the tail kernels' template parameter: eps and step share instantiation 0 (a.step_mode tells them apart at
+// run time); every other mode has its own.
+constexpr int tail_epi(int mode) { return mode <= kTailStep ? 0 : mode - 1; }
+// ... and back: the one mode of instantiation epi >= 1, eps or step for 0
+constexpr TailMode tail_epi_mode(int epi, bool step) { return epi ? TailMode(epi + 1) : step ? kTailStep : kTailEps; }
+// what a mode does
+constexpr bool tail_reads_x(int mode) { return mode != kTailEps && mode != kTailSse; }
+constexpr bool tail_loads_row(int mode) {  // row *tsel of the schedule tables and the run's parameters
+  return mode == kTailStep || mode == kTailX0Step || mode == kTailX0StepMom;
+}
+constexpr bool tail_x0_form(int mode) { return mode == kTailX0Step || mode == kTailX0StepMom; }
+// the block statistics it ends in (tail_block_stats: 2 sums; 2 sums, min, max), 0 where it ends in none
+constexpr int tail_stats(int mode) { return mode == kTailSse ? 2 : mode == kTailX0StepMom ? 4 : 0; }
+
 struct TailArgs {
   const void* g;        // NHWC [nb][H][W][C] : silu(gn(h))
   const float* w;       // [3][C][3][3] fp32 (reference layout)
@@ -391,9 +420,7 @@ struct TailArgs {
   float guide_w;        // w (fp32 cast of the Python float)
   float guide_w1;       // (1 + w) computed in double then cast, as the reference's scalar
   // mode
-  int step_mode;        // 0: write eps NCHW; 1: sampler update of x in place; 2: x0_out = clip(a0 x - b0 eps) (x read only);
-                        // 3: the x0-form update of x in place (rows of xrow, below); 4: the denoising-error sums;
-                        // 5: step 3 plus the x0 moments of every image (last fields, below)
+  int step_mode;        // a TailMode (an int: the argument block's layout is fixed, below)
   float* eps_out;       // NCHW [n][3][H][W]
   float* x;             // NCHW [n][3][H][W]
   const int* tsel;      // current step t (device)
@@ -407,26 +434,26 @@ struct TailArgs {
   // (k = tap*C + ci; k-step ks, lane group kg, output channel, 8 consecutive k)
   const float* coef;
   const bf16_t* wmf;
-  // step_mode 2 (itsd_sampler_predict_x0): a0 = 1/sqrt(abar_t), b0 = sqrt(1/abar_t - 1) as fp32, output NCHW [n][3][H][W]
+  // kTailX0 (itsd_sampler_predict_x0): a0 = 1/sqrt(abar_t), b0 = sqrt(1/abar_t - 1) as fp32, output NCHW [n][3][H][W]
   float a0, b0;
   float* x0_out;
-  // step_mode 3 (itsd_sampler_run under an x0-form schedule, itsd_set_schedule_x0): row k = *tsel of five device
+  // kTailX0Step (itsd_sampler_run under an x0-form schedule, itsd_set_schedule_x0): row k = *tsel of five device
   // tables [K] -- a0, b0, c0, cx, sg in this order -- and whether the x_0 estimate is clipped. tsel, noise (indexed by
-  // row), run and nan_flag as in step_mode 1; coeff1 / coeff2 / sqrt_var are not read
+  // row), run and nan_flag as in kTailStep; coeff1 / coeff2 / sqrt_var are not read
   const float* xrow[5];
   int clip_x0;
-  // step_mode 4 (itsd_verify_denoise): the denoising-error probe. Nothing is guided and nothing of the step's is read:
+  // kTailSse (itsd_verify_denoise): the denoising-error probe. Nothing is guided and nothing of the step's is read:
   // z[e] = noise[e] (here ONE field [3][H][W], shared by every image) or Philox (vseed, vstream, e), e the element
   // within the image; each block stores its (sum (z - eps_c)^2, sum (z - eps_u)^2) as one fp32 pair at
-  // vpart[blockIdx.x] (blocks are image-major and never straddle two images) and tail_sse_finalize_kernel sums each
+  // vpart[blockIdx.x] (blocks are image-major and never straddle two images) and tail_stats_finalize_kernel sums each
   // image's pairs in block order in fp64 into vsse[n][2]. eps_out, when non-null, receives the unguided
   // eps [1 or 2][n][3][H][W] (cond, then uncond). x is not read.
-  // step_mode 5 (itsd_sampler_run with a score trace attached, itsd_sampler_set_trace): step_mode 3 on x, bit for bit,
-  // and each block stores (sum x0, sum x0^2, min x0, max x0) of its output elements -- x0 the value the step used,
+  // kTailX0StepMom (itsd_sampler_run with a score trace attached, itsd_sampler_set_trace): kTailX0Step on x, bit for
+  // bit, and each block stores (sum x0, sum x0^2, min x0, max x0) of its output elements -- x0 the value the step used,
   // clipped iff clip_x0 -- as four fp32 at tpart[blockIdx.x] (blocks are image-major and never straddle two images);
-  // tail_mom_finalize_kernel folds each image's blocks in block order in fp64 into
+  // tail_stats_finalize_kernel folds each image's blocks in block order in fp64 into
   // trace[(*tsel * trace_stride + img) * 4 + 0..3], for a row *tsel in [0, trace_rows).
-  // Its operands share the storage of step_mode 4's, which it never reads (and the reverse), and trace_stride sits in
+  // Its operands share the storage of kTailSse's, which it never reads (and the reverse), and trace_stride sits in
   // what was padding: the struct keeps its size and offsets. The struct is the kernels' argument block, and a larger
   // one changed the register allocation of the existing tail_mfma_kernel instantiations.
   unsigned long long vseed;

@@ -1418,49 +1418,59 @@ __device__ __forceinline__ float philox_normal(unsigned long long seed, unsigned
 // ============================================================================ tail conv + sampler step
 // tail = GN -> Swish -> Conv2d(C, 3, 3, padding=1) (Model.py:252-256, 282). The GN+Swish
 // output g is produced by groupnorm_kernel (tail_mfma_kernel applies it itself); the three kernels below do the
-// 3-output conv per pixel and hand each output element's eps to tail_finish (tail_sse_item for the last), which ends in
-// one of six ways:
-//   eps  (TailArgs::step_mode 0, the forward API)  eps_out = eps
-//   step (step_mode 1)  the ancestral update of Diffusion.py:67-71,96-100 in place on x:
+// 3-output conv per pixel and hand each output element's unguided eps pair to tail_item, the one epilogue of all three,
+// which ends in one of six ways (TailArgs::step_mode, a TailMode of common.h):
+//   eps  (kTailEps, the forward API)  eps_out = eps
+//   step (kTailStep)  the ancestral update of Diffusion.py:67-71,96-100 in place on x:
 //          mean = coeff1[t]*x - coeff2[t]*eps ;  x = mean + sqrt(var[t]) * z  (z = 0 at t = 0; injected or Philox),
 //          clipped to [-1, 1] at step RunParams::clip_at; a NaN (tested before the clip) is reported to the caller,
 //          which raises nan_flag
-//   x0   (step_mode 2, its own instantiation: the eps / step kernels' code is what it was)
+//   x0   (kTailX0, its own instantiation: the eps / step kernels' code is what it was)
 //          x0_out = clip(a0 * x - b0 * eps, -1, 1)   (the x_0 estimate of the state x at this step)
 //          x is only read, no noise is drawn, the NaN flag is not touched, a.run and the schedule tables are not read.
-//   x0 step (step_mode 3, its own instantiation as well)  DDIM(eta) through the x_0 estimate, in place on x, with the
+//   x0 step (kTailX0Step, its own instantiation as well)  DDIM(eta) through the x_0 estimate, in place on x, with the
 //          scalars of row k = *tsel of the five TailArgs::xrow tables:
 //          x0 = a0*x - b0*eps, clipped to [-1, 1] iff clip_x0 ;  m = (c0*x0) + (cx*x) ;  x = sg != 0 ? m + sg*z : m
 //          (no contraction: the tests demand these bits). z is noise[k] or Philox (seed, k, noise_offset + o); where
 //          sg == 0 it is neither drawn nor read (wave-uniform: one row a launch). NaN test, clip_at clip and the
 //          flag as in the ancestral step.
-//   sse  (step_mode 4, its own instantiation too)  the denoising-error probe of itsd_verify_denoise: with z[e] the
+//   sse  (kTailSse, its own instantiation too)  the denoising-error probe of itsd_verify_denoise: with z[e] the
 //          probe's noise at element e = o mod 3HW of the image (noise[e], or Philox (vseed, vstream, e): one field
 //          shared by every image), q_c = (z - eps_c)^2 and, CFG, q_u = (z - eps_u)^2 in fp32 without contraction --
 //          NOT guided: the two branches stay apart. x is neither read nor written; the NaN flag, the step counter,
 //          a.run and the schedule tables are not touched. Each block sums its items' q in an order fixed by the
 //          item's place in the block (the thread's own items in order, a lane butterfly, then the wave partials in
-//          wave order by thread 0: tail_sse_block) and stores one fp32 pair to vpart[blockIdx.x] with a plain store;
-//          tail_sse_finalize_kernel adds each image's pairs in block order in fp64. No atomics: a sum is a function
+//          wave order by thread 0: tail_block_stats) and stores one fp32 pair to vpart[blockIdx.x] with a plain store;
+//          tail_stats_finalize_kernel adds each image's pairs in block order in fp64. No atomics: a sum is a function
 //          of (image, label, z) alone, whatever the batch or the image's place in it. eps_out (debug, NULL in
 //          production) receives the unguided eps [1 or 2][n][3][H][W].
 // CFG: eps = (1+w) eps_c - w eps_u (DiffusionCondition.py:85) with the unconditional
-// branch at image index img + n of g (guided before tail_finish, in every mode but sse).
-//   x0 step + moments (step_mode 5, its own instantiation)  the x0 step, the same expressions in the same order on the
+// branch at image index img + n of g (guided by tail_item before tail_finish, in every mode but sse).
+//   x0 step + moments (kTailX0StepMom, its own instantiation)  the x0 step, the same expressions in the same order on the
 //          same x (bit-identical new x), and each output element's x0 -- the value the step used, clipped iff
 //          clip_x0; CFG: of the guided step, the n candidates only -- added to the thread's (sum, sum of squares, min,
-//          max), reduced by tail_mom_block (tail_sse_block's tree) into tpart[blockIdx.x][4]; tail_mom_finalize_kernel
-//          folds each image's blocks in block order in fp64 into row *tsel of the caller's trace. No atomics.
-// EPI, the kernels' template parameter, names the instantiation: 0 eps / step, 1 x0, 2 x0 step, 3 sse, 4 x0 step +
-// moments.
+//          max), reduced by tail_block_stats (the sse sums' tree, on four values) into tpart[blockIdx.x][4];
+//          tail_stats_finalize_kernel folds each image's blocks in block order in fp64 into row *tsel of the caller's
+//          trace. No atomics.
+// EPI, the kernels' template parameter, names the instantiation (tail_epi of common.h): 0 eps / step, 1 x0, 2 x0 step,
+// 3 sse, 4 x0 step + moments. Each kernel ends in one loop over its output items, which calls tail_item, and one call
+// of tail_block_stats, which every thread of the block reaches and which is empty where the mode ends in no statistics.
 __device__ __forceinline__ float tail_x0(float a0, float b0, float xv, float e) {
 #pragma clang fp contract(off)
   const float v = a0 * xv - b0 * e;
   return fminf(fmaxf(v, -1.0f), 1.0f);
 }
 
-// The step's scalars: row t of the schedule tables and the run's parameters. Loaded in the two step modes only (the
-// x0 step: c1, c2, sv hold the row's c0, cx, sg, and a0, b0 its x_0 coefficients); the other two modes read none of
+// An instantiation's mode: eps or step for EPI 0, told apart by a.step_mode; the one mode of every other EPI ...
+template <int EPI>
+__device__ __forceinline__ TailMode tail_mode(const TailArgs& a) {
+  return tail_epi_mode(EPI, a.step_mode != 0);
+}
+// ... and what the compiler knows of it, for the tests that do not tell eps from step
+template <int EPI> constexpr TailMode kTailMode = tail_epi_mode(EPI, false);
+
+// The step's scalars: row t of the schedule tables and the run's parameters. Loaded in the step modes only (the
+// x0 step: c1, c2, sv hold the row's c0, cx, sg, and a0, b0 its x_0 coefficients); the other modes read none of
 // them.
 struct TailStep {
   int t = 0;
@@ -1473,12 +1483,12 @@ struct TailStep {
 template <int EPI>
 __device__ __forceinline__ TailStep tail_step_load(const TailArgs& a) {
   TailStep s;
-  if (EPI == 2 || EPI == 4 || (EPI == 0 && a.step_mode)) {
+  if (tail_loads_row(tail_mode<EPI>(a))) {
     s.t = *a.tsel;
     s.seed = a.run->seed;
     s.noise_offset = a.run->noise_offset;
     s.clip_at = a.run->clip_at;
-    if constexpr (EPI == 2 || EPI == 4) {
+    if constexpr (tail_x0_form(kTailMode<EPI>)) {
       s.a0 = a.xrow[0][s.t];
       s.b0 = a.xrow[1][s.t];
       s.c1 = a.xrow[2][s.t];
@@ -1493,10 +1503,10 @@ __device__ __forceinline__ TailStep tail_step_load(const TailArgs& a) {
   return s;
 }
 
-// x at NCHW offset o where the epilogue reads it (the eps mode has no x)
+// x at NCHW offset o where the epilogue reads it (the eps and sse modes have no x)
 template <int EPI>
 __device__ __forceinline__ float tail_x(const TailArgs& a, size_t o) {
-  return (EPI || a.step_mode) ? a.x[o] : 0.f;
+  return tail_reads_x(tail_mode<EPI>(a)) ? a.x[o] : 0.f;
 }
 
 // NCHW offset of output channel oc at pixel opx of a block of full rows that starts at row y0 of image img
@@ -1505,32 +1515,33 @@ __device__ __forceinline__ size_t tail_offset(int img, int y0, int opx, int oc, 
   return ((size_t)img * 3 + oc) * (H * W) + rem;
 }
 
-// The moments epilogue's running (sum x0, sum x0^2, min x0, max x0) of a thread, a wave or a block. A thread without
-// items keeps the neutral element.
+// A thread's running statistics of its items, the four tail_block_stats reduces: the moments epilogue's (sum x0,
+// sum x0^2, min x0, max x0); the sse epilogue's two sums in s and q. A thread without items keeps the neutral element.
 struct TailMom {
   float s = 0.f, q = 0.f, lo = INFINITY, hi = -INFINITY;
 };
 
 // One output element: its (guided) eps e, its NCHW offset o, its x value xv (tail_x) and the step's scalars. Returns
-// whether the step's new x is NaN (false in the other two modes). EPI 4 is EPI 2's step, expression for expression,
-// and adds the x0 the step used to the thread's moments mom (fp32, no contraction, the thread's items in call order).
+// whether the step's new x is NaN (false in the modes without a step). The moments mode is the x0 step, the one
+// expression, and adds the x0 the step used to the thread's moments mom (fp32, no contraction, the thread's items in
+// call order).
 template <int EPI>
 __device__ __forceinline__ bool tail_finish(const TailArgs& a, const TailStep& s, size_t o, float xv, float e,
-                                            TailMom* mom = nullptr) {
+                                            TailMom& mom) {
 #pragma clang fp contract(off)
-  if constexpr (EPI == 1) {
+  if constexpr (kTailMode<EPI> == kTailX0) {
     a.x0_out[o] = tail_x0(a.a0, a.b0, xv, e);
     return false;
   }
-  if constexpr (EPI == 2 || EPI == 4) {
+  if constexpr (tail_x0_form(kTailMode<EPI>)) {
     float x0 = s.a0 * xv - s.b0 * e;
     if (a.clip_x0) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-    if constexpr (EPI == 4) {
+    if constexpr (kTailMode<EPI> == kTailX0StepMom) {
       const float sq = x0 * x0;
-      mom->s = mom->s + x0;
-      mom->q = mom->q + sq;
-      mom->lo = fminf(mom->lo, x0);
-      mom->hi = fmaxf(mom->hi, x0);
+      mom.s = mom.s + x0;
+      mom.q = mom.q + sq;
+      mom.lo = fminf(mom.lo, x0);
+      mom.hi = fmaxf(mom.hi, x0);
     }
     float xn = (s.c1 * x0) + (s.c2 * xv);
     if (s.sv != 0.f) {  // (one row a launch: uniform)
@@ -1543,7 +1554,7 @@ __device__ __forceinline__ bool tail_finish(const TailArgs& a, const TailStep& s
     a.x[o] = xn;
     return bad;
   }
-  if (!a.step_mode) {
+  if (tail_mode<EPI>(a) == kTailEps) {
     a.eps_out[o] = e;
     return false;
   }
@@ -1581,58 +1592,63 @@ __device__ __forceinline__ void tail_sse_item(const TailArgs& a, size_t o, int i
   }
 }
 
-// The sse epilogue's block reduction, reached by every thread of the block (NW waves): lane butterfly, the wave
-// partials through LDS (scratch: >= 2 NW floats of the block's shared memory that nothing reads any more once every
-// thread is here), summed in wave order by thread 0, one plain store of the pair.
-template <int NW>
-__device__ __forceinline__ void tail_sse_block(const TailArgs& a, float* scratch, float qc, float qu) {
-  qc = wave_sum(qc);
-  qu = wave_sum(qu);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) {
-    scratch[(threadIdx.x >> 6) * 2] = qc;
-    scratch[(threadIdx.x >> 6) * 2 + 1] = qu;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float sc = scratch[0], su = scratch[1];
-    for (int w = 1; w < NW; ++w) {
-      sc += scratch[2 * w];
-      su += scratch[2 * w + 1];
+// The epilogue of all three kernels, once per output item: the item's unguided pair (ec; eu(), a callable evaluated
+// for CFG only, so that the kernel's work for the uncond value stays inside that branch), its NCHW offset o in image
+// img, its x value xv and the step's scalars. The sse mode keeps the pair apart; every other mode guides it (no
+// contraction, this operand order) and ends in tail_finish. Returns whether the step's new x is NaN.
+template <int EPI, typename EU>
+__device__ __forceinline__ bool tail_item(const TailArgs& a, const TailStep& s, size_t o, int img, float xv, float ec,
+                                          EU&& eu, TailMom& mom) {
+  if constexpr (kTailMode<EPI> == kTailSse) {
+    tail_sse_item(a, o, img, ec, a.cfg ? eu() : 0.f, mom.s, mom.q);
+    return false;
+  } else {
+    float e = ec;
+    if (a.cfg) {
+#pragma clang fp contract(off)
+      const float u = eu();
+      e = a.guide_w1 * e - a.guide_w * u;
     }
-    a.vpart[(size_t)blockIdx.x * 2] = sc;
-    a.vpart[(size_t)blockIdx.x * 2 + 1] = su;
+    return tail_finish<EPI>(a, s, o, xv, e, mom);
   }
 }
 
-// The moments epilogue's block reduction, tail_sse_block's tree on four values: reached by every thread of the block
-// (NW waves), lane butterfly (sums by +, min / max by fminf / fmaxf), the wave partials through LDS (scratch: >= 4 NW
-// floats nothing reads any more), folded in wave order by thread 0, one plain store of the four floats.
-template <int NW>
-__device__ __forceinline__ void tail_mom_block(const TailArgs& a, float* scratch, TailMom m) {
-  m.s = wave_sum(m.s);
-  m.q = wave_sum(m.q);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    m.lo = fminf(m.lo, __shfl_xor(m.lo, o, 64));
-    m.hi = fmaxf(m.hi, __shfl_xor(m.hi, o, 64));
-  }
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) {
-    float* p = scratch + (threadIdx.x >> 6) * 4;
-    p[0] = m.s; p[1] = m.q; p[2] = m.lo; p[3] = m.hi;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float s = scratch[0], q = scratch[1], lo = scratch[2], hi = scratch[3];
-    for (int w = 1; w < NW; ++w) {
-      s += scratch[4 * w];
-      q += scratch[4 * w + 1];
-      lo = fminf(lo, scratch[4 * w + 2]);
-      hi = fmaxf(hi, scratch[4 * w + 3]);
+// One slot of the block statistics: 0 and 1 are sums, 2 a minimum, 3 a maximum
+__device__ __forceinline__ float tail_stat_fold(int k, float v, float w) {
+  return k < 2 ? v + w : k == 2 ? fminf(v, w) : fmaxf(v, w);
+}
+
+// The block reduction of the modes that end in statistics (N = tail_stats(mode): the first N fields of TailMom; empty
+// for N = 0), reached by every thread of the block (NW waves): lane butterfly, the wave partials through LDS (scratch:
+// >= N NW floats of the block's shared memory that nothing reads any more once every thread is here), folded in wave
+// order by thread 0, one plain store of the N floats to part[blockIdx.x][N]. One tree for both modes, so one rounding
+// bound (the tests' L_CHAIN).
+template <int NW, int N>
+__device__ __forceinline__ void tail_block_stats(const TailArgs& a, float* scratch, const TailMom& m) {
+  static_assert(N == 0 || N == 2 || N == 4, "sse pair or the four moments");
+  if constexpr (N != 0) {
+    float v[4] = {wave_sum(m.s), wave_sum(m.q), 0.f, 0.f};
+    if constexpr (N == 4) {
+      v[2] = wave_min(m.lo);
+      v[3] = wave_max(m.hi);
     }
-    float* p = a.tpart + (size_t)blockIdx.x * 4;
-    p[0] = s; p[1] = q; p[2] = lo; p[3] = hi;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+      for (int k = 0; k < N; ++k) scratch[(threadIdx.x >> 6) * N + k] = v[k];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+      for (int k = 0; k < N; ++k) v[k] = scratch[k];
+      for (int w = 1; w < NW; ++w) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) v[k] = tail_stat_fold(k, v[k], scratch[N * w + k]);
+      }
+      float* part = N == 2 ? a.vpart : a.tpart;
+#pragma unroll
+      for (int k = 0; k < N; ++k) part[(size_t)blockIdx.x * N + k] = v[k];
+    }
   }
 }
 
@@ -1685,43 +1701,20 @@ __global__ __launch_bounds__(256) void tail_kernel(TailArgs a) {
     }
     e0 = s0 + a.b[0]; e1 = s1 + a.b[1]; e2 = s2 + a.b[2];
   };
-  float eps[3];
+  float eps[3], u[3] = {0.f, 0.f, 0.f};
   conv3(img, eps[0], eps[1], eps[2]);
-  if constexpr (EPI == 3) {  // (the launcher admits H W % 256 == 0 only: no thread returned above)
-    float u[3] = {0.f, 0.f, 0.f}, qc = 0.f, qu = 0.f;
-    if (a.cfg) conv3(img + a.n, u[0], u[1], u[2]);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) tail_sse_item(a, ((size_t)img * 3 + c) * HW + rem, img, eps[c], u[c], qc, qu);
-    tail_sse_block<4>(a, wl, qc, qu);
-    return;
-  }
-  if (a.cfg) {
-#pragma clang fp contract(off)
-    float u[3];
-    conv3(img + a.n, u[0], u[1], u[2]);
-    const float w1 = a.guide_w1;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) eps[c] = w1 * eps[c] - a.guide_w * u[c];
-  }
+  if (a.cfg) conv3(img + a.n, u[0], u[1], u[2]);
   const TailStep st = tail_step_load<EPI>(a);
+  TailMom mom;
   bool bad = false;
-  if constexpr (EPI == 4) {  // (H W % 256 == 0 only, as EPI 3: every thread of the block is here)
-    TailMom mom;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const size_t o = ((size_t)img * 3 + c) * HW + rem;
-      bad |= tail_finish<EPI>(a, st, o, tail_x<EPI>(a, o), eps[c], &mom);
-    }
-    if (bad) atomicOr(a.nan_flag, 1);
-    tail_mom_block<4>(a, wl, mom);
-    return;
-  }
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     const size_t o = ((size_t)img * 3 + c) * HW + rem;
-    bad |= tail_finish<EPI>(a, st, o, tail_x<EPI>(a, o), eps[c]);
+    bad |= tail_item<EPI>(a, st, o, img, tail_x<EPI>(a, o), eps[c], [&] { return u[c]; }, mom);
   }
   if (bad) atomicOr(a.nan_flag, 1);
+  // (the launcher admits the modes with statistics at H W % 256 == 0 only: no thread of theirs returned above)
+  tail_block_stats<4, tail_stats(kTailMode<EPI>)>(a, wl, mom);
 }
 
 // Tiled tail: one block per 64 output pixels (64/W full rows of one image); the input
@@ -1786,59 +1779,19 @@ __global__ __launch_bounds__(256) void tail2_kernel(TailArgs a) {
     rp[0] = s0; rp[1] = s1; rp[2] = s2;
   }
   __syncthreads();
-  if constexpr (EPI == 3) {  // as below, the two branches kept apart; threads 192.. hold no item
-    float qc = 0.f, qu = 0.f;
-    if (tid < 192) {
-      const int opx = tid / 3, oc = tid - opx * 3;
-      float s = 0.f, su = 0.f;
-      for (int w = 0; w < 4; ++w) s += red[(w * 64 + opx) * 3 + oc];
-      if (a.cfg)
-        for (int w = 0; w < 4; ++w) su += red[((4 + w) * 64 + opx) * 3 + oc];
-      tail_sse_item(a, tail_offset(img, y0, opx, oc, H, W), img, a.b[oc] + s, a.b[oc] + su, qc, qu);
-    }
-    tail_sse_block<4>(a, wl, qc, qu);
-    return;
+  TailMom mom;
+  if (tid < 192) {  // one item: (pixel, output channel), channel quarters summed in order; threads 192.. hold none
+    const int opx = tid / 3, oc = tid - opx * 3;
+    const auto e = [&](int pass) {
+      float s = 0.f;
+      for (int w = 0; w < 4; ++w) s += red[((pass * 4 + w) * 64 + opx) * 3 + oc];
+      return a.b[oc] + s;
+    };
+    const size_t o = tail_offset(img, y0, opx, oc, H, W);
+    if (tail_item<EPI>(a, tail_step_load<EPI>(a), o, img, tail_x<EPI>(a, o), e(0), [&] { return e(1); }, mom))
+      atomicOr(a.nan_flag, 1);
   }
-  if constexpr (EPI == 4) {  // the step below, word for word, on threads 0..191; every thread reaches the reduction
-    TailMom mom;
-    if (tid < 192) {
-      const int opx = tid / 3, oc = tid - opx * 3;
-      float e = a.b[oc];
-      {
-        float s = 0.f;
-        for (int w = 0; w < 4; ++w) s += red[(w * 64 + opx) * 3 + oc];
-        e += s;
-      }
-      if (a.cfg) {
-#pragma clang fp contract(off)
-        float s = 0.f;
-        for (int w = 0; w < 4; ++w) s += red[((4 + w) * 64 + opx) * 3 + oc];
-        const float u = a.b[oc] + s;
-        e = a.guide_w1 * e - a.guide_w * u;
-      }
-      const size_t o = tail_offset(img, y0, opx, oc, H, W);
-      if (tail_finish<EPI>(a, tail_step_load<EPI>(a), o, tail_x<EPI>(a, o), e, &mom)) atomicOr(a.nan_flag, 1);
-    }
-    tail_mom_block<4>(a, wl, mom);
-    return;
-  }
-  if (tid >= 192) return;
-  const int opx = tid / 3, oc = tid - opx * 3;  // (pixel, output channel), channel quarters summed in order
-  float e = a.b[oc];
-  {
-    float s = 0.f;
-    for (int w = 0; w < 4; ++w) s += red[(w * 64 + opx) * 3 + oc];
-    e += s;
-  }
-  if (a.cfg) {
-#pragma clang fp contract(off)
-    float s = 0.f;
-    for (int w = 0; w < 4; ++w) s += red[((4 + w) * 64 + opx) * 3 + oc];
-    const float u = a.b[oc] + s;
-    e = a.guide_w1 * e - a.guide_w * u;
-  }
-  const size_t o = tail_offset(img, y0, opx, oc, H, W);
-  if (tail_finish<EPI>(a, tail_step_load<EPI>(a), o, tail_x<EPI>(a, o), e)) atomicOr(a.nan_flag, 1);
+  tail_block_stats<4, tail_stats(kTailMode<EPI>)>(a, wl, mom);
 }
 
 // bf16 tail on MFMA with the tail GroupNorm+SiLU fused (Model.py:252-256 / 282, then the
@@ -1885,7 +1838,7 @@ __global__ __launch_bounds__(NTH, 2) void tail_mfma_kernel(TailArgs a) {
   constexpr int TIT = (TM_PX * 3 + NTH - 1) / NTH;
   float xpre[TIT] = {};
   TailStep st;
-  if ((EPI || a.step_mode) && EPI != 3) {
+  if (tail_reads_x(tail_mode<EPI>(a))) {
     st = tail_step_load<EPI>(a);
 #pragma unroll
     for (int k = 0; k < TIT; ++k) {
@@ -1976,51 +1929,17 @@ __global__ __launch_bounds__(NTH, 2) void tail_mfma_kernel(TailArgs a) {
     }
   }
   __syncthreads();
-  if constexpr (EPI == 3) {  // the red[] rows of both passes, unguided
-    float qc = 0.f, qu = 0.f;
+  TailMom mom;
 #pragma unroll
-    for (int k = 0; k < TIT; ++k) {
-      const int it = tid + NTH * k;
-      if (it >= TM_PX * 3) break;
-      const int opx = it / 3, oc = it - opx * 3;
-      const float ec = red[opx * 3 + oc] + a.b[oc];
-      const float eu = a.cfg ? red[(TM_PX + opx) * 3 + oc] + a.b[oc] : 0.f;
-      tail_sse_item(a, tail_offset(img, y0, opx, oc, H, W), img, ec, eu, qc, qu);
-    }
-    tail_sse_block<NW>(a, (float*)tsm, qc, qu);
-    return;
-  }
-  if constexpr (EPI == 4) {  // the loop below, word for word, with the thread's moments
-    TailMom mom;
-#pragma unroll
-    for (int k = 0; k < TIT; ++k) {
-      const int it = tid + NTH * k;
-      if (it >= TM_PX * 3) break;
-      const int opx = it / 3, oc = it - opx * 3;
-      float e = red[opx * 3 + oc] + a.b[oc];
-      if (a.cfg) {
-#pragma clang fp contract(off)
-        const float u = red[(TM_PX + opx) * 3 + oc] + a.b[oc];
-        e = a.guide_w1 * e - a.guide_w * u;
-      }
-      if (tail_finish<EPI>(a, st, tail_offset(img, y0, opx, oc, H, W), xpre[k], e, &mom)) atomicOr(a.nan_flag, 1);
-    }
-    tail_mom_block<NW>(a, (float*)tsm, mom);
-    return;
-  }
-#pragma unroll
-  for (int k = 0; k < TIT; ++k) {
+  for (int k = 0; k < TIT; ++k) {  // the red[] rows of both passes
     const int it = tid + NTH * k;
     if (it >= TM_PX * 3) break;
     const int opx = it / 3, oc = it - opx * 3;
-    float e = red[opx * 3 + oc] + a.b[oc];
-    if (a.cfg) {
-#pragma clang fp contract(off)
-      const float u = red[(TM_PX + opx) * 3 + oc] + a.b[oc];
-      e = a.guide_w1 * e - a.guide_w * u;
-    }
-    if (tail_finish<EPI>(a, st, tail_offset(img, y0, opx, oc, H, W), xpre[k], e)) atomicOr(a.nan_flag, 1);
+    const float ec = red[opx * 3 + oc] + a.b[oc];
+    const auto eu = [&] { return red[(TM_PX + opx) * 3 + oc] + a.b[oc]; };
+    if (tail_item<EPI>(a, st, tail_offset(img, y0, opx, oc, H, W), img, xpre[k], ec, eu, mom)) atomicOr(a.nan_flag, 1);
   }
+  tail_block_stats<NW, tail_stats(kTailMode<EPI>)>(a, (float*)tsm, mom);
 }
 
 constexpr size_t kTailSmemMax = 160 * 1024;  // the dynamic shared memory a tail kernel may ask for
@@ -2036,92 +1955,88 @@ static bool tail_mfma_ok_px(int px, int H, int W, int C) {
 size_t tail_mfma_smem(int H, int W, int C) { return tail_mfma_smem_px(128, H, W, C); }
 bool tail_mfma_ok(int H, int W, int C) { return tail_mfma_ok_px(128, H, W, C); }
 
-// step_mode 4's second launch: sse[img][k] = sum over the image's bpi block pairs, in block order, in fp64
-__global__ __launch_bounds__(64) void tail_sse_finalize_kernel(const float* part, int bpi, int n2, double* sse) {
+// The second launch of the modes that end in statistics (N = tail_stats(mode)): thread (img, k) folds the image's bpi
+// block partials part[block][N] in block order in fp64 (k = 0, 1: sums; 2: min; 3: max) into
+// out[rows][stride][N] at row *tsel (the moments' trace; the launch runs before the step counter's decrement, so the
+// row is the one the tail just ran, and a row outside the buffer is not written) or, without tsel, row 0 (the sse
+// pairs' vsse[n][2]).
+__global__ __launch_bounds__(64) void tail_stats_finalize_kernel(const float* part, int bpi, int n, int N,
+                                                                 const int* tsel, double* out, int rows, int stride) {
   const int i = blockIdx.x * 64 + threadIdx.x;
-  if (i >= n2) return;
-  const float* p = part + (size_t)(i >> 1) * bpi * 2 + (i & 1);
-  double s = 0.0;
-  for (int b = 0; b < bpi; ++b) s += (double)p[2 * b];
-  sse[i] = s;
-}
-
-// step_mode 5's second launch: thread (img, k) folds the image's bpi block partials part[block][4] in block order in
-// fp64 (k = 0, 1: sums; 2: min; 3: max) into row *tsel of trace[rows][stride][4]. It runs before the step counter's
-// decrement, so the row is the one the tail just ran; a row outside the buffer is not written.
-__global__ __launch_bounds__(64) void tail_mom_finalize_kernel(const float* part, int bpi, int n, const int* tsel,
-                                                               double* trace, int rows, int stride) {
-  const int i = blockIdx.x * 64 + threadIdx.x;
-  if (i >= 4 * n) return;
-  const int row = *tsel;
+  if (i >= N * n) return;
+  const int row = tsel ? *tsel : 0;
   if (row < 0 || row >= rows) return;
-  const int img = i >> 2, k = i & 3;
-  const float* p = part + (size_t)img * bpi * 4 + k;
+  const int img = i / N, k = i - img * N;
+  const float* p = part + (size_t)img * bpi * N + k;
   double v = (double)p[0];
   for (int b = 1; b < bpi; ++b) {
-    const double w = (double)p[4 * b];
+    const double w = (double)p[N * b];
     v = k < 2 ? v + w : k == 2 ? fmin(v, w) : fmax(v, w);
   }
-  trace[((size_t)row * stride + img) * 4 + k] = v;
+  out[((size_t)row * stride + img) * N + k] = v;
 }
 
-// step_mode 2 needs its operands (and nothing of the step's); step_mode 3 its tables and the step's run state;
-// step_mode 4 its two outputs; step_mode 5 what 3 needs and a trace that holds the batch
+// kTailX0 needs its operands (and nothing of the step's); the x0-form step its tables and the step's run state;
+// kTailSse its two outputs; kTailX0StepMom what the x0-form step needs and a trace that holds the batch
 static bool tail_x0_ok(const TailArgs& a) {
-  if (a.step_mode == 4) return a.vpart && a.vsse;
-  if (a.step_mode == 5 && !(a.tpart && a.trace && a.trace_rows >= 1 && a.trace_stride >= a.n)) return false;
-  if (a.step_mode == 3 || a.step_mode == 5) {
+  if (a.step_mode < kTailEps || a.step_mode > kTailX0StepMom) return false;
+  if (a.step_mode == kTailSse) return a.vpart && a.vsse;
+  if (a.step_mode == kTailX0StepMom && !(a.tpart && a.trace && a.trace_rows >= 1 && a.trace_stride >= a.n))
+    return false;
+  if (tail_x0_form(a.step_mode)) {
     for (const float* p : a.xrow)
       if (!p) return false;
     return a.x && a.tsel && a.run && a.nan_flag && (a.clip_x0 == 0 || a.clip_x0 == 1);
   }
-  return a.step_mode != 2 || (a.x && a.x0_out);
+  return a.step_mode != kTailX0 || (a.x && a.x0_out);
 }
 
-// The body of a tail launcher from its launch geometry on: launches the instantiation a.step_mode selects (X0K for the
-// x0 epilogue, XSK for the x0-form step, SSEK for the denoising-error sums, MOMK for the x0-form step with moments,
-// PLAIN for eps and step; each under its own name, which the census and the profiles key on) and returns the launch's
-// status. BIG: the five may use up to kTailSmemMax of dynamic shared memory; the attribute is set once. SSEK and MOMK
-// are followed by their finalize launches, and are refused where a block would straddle two images (the grid is not a
-// whole number of blocks an image).
-#define ITSD_RETURN_TAIL_LAUNCH(PLAIN, X0K, XSK, SSEK, MOMK, BIG, grid, block, sm, s, a)                       \
-  do {                                                                                                         \
-    static bool attr = !(BIG);                                                                                 \
-    if (!attr) {                                                                                               \
-      for (const void* f : {(const void*)PLAIN, (const void*)X0K, (const void*)XSK, (const void*)SSEK,         \
-                            (const void*)MOMK}) {                                                              \
-        hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTailSmemMax);  \
-        if (e != hipSuccess) return e;                                                                         \
-      }                                                                                                        \
-      attr = true;                                                                                             \
-    }                                                                                                          \
-    if ((a).step_mode == 4) {                                                                                  \
-      if ((a).n < 1 || (grid).x % (a).n) return hipErrorInvalidValue;                                          \
-      ITSD_LAUNCH(SSEK, grid, block, sm, s, a);                                                                \
-      ITSD_LAUNCH(tail_sse_finalize_kernel, dim3((2 * (a).n + 63) / 64), dim3(64), 0, s, (a).vpart,            \
-                  (int)((grid).x / (a).n), 2 * (a).n, (a).vsse);                                               \
-      return hipGetLastError();                                                                                \
-    }                                                                                                          \
-    if ((a).step_mode == 5) {                                                                                  \
-      if ((a).n < 1 || (grid).x % (a).n) return hipErrorInvalidValue;                                          \
-      ITSD_LAUNCH(MOMK, grid, block, sm, s, a);                                                                \
-      ITSD_LAUNCH(tail_mom_finalize_kernel, dim3((4 * (a).n + 63) / 64), dim3(64), 0, s, (a).tpart,            \
-                  (int)((grid).x / (a).n), (a).n, (a).tsel, (a).trace, (a).trace_rows, (a).trace_stride);      \
-      return hipGetLastError();                                                                                \
-    }                                                                                                          \
-    if ((a).step_mode == 2) ITSD_LAUNCH(X0K, grid, block, sm, s, a);                                           \
-    else if ((a).step_mode == 3) ITSD_LAUNCH(XSK, grid, block, sm, s, a);                                      \
-    else ITSD_LAUNCH(PLAIN, grid, block, sm, s, a);                                                            \
-    return hipGetLastError();                                                                                  \
+using TailKernel = void (*)(TailArgs);
+template <int E> using TailEpi = std::integral_constant<int, E>;
+
+// The body of a tail launcher from its launch geometry on: launches the instantiation a.step_mode selects of one kernel
+// family and returns the launch's status. FAMILY names the family, an expression in E, the instantiation's EPI; PLAIN
+// is its E = 0 member once more, spelled as the census has always recorded it (ITSD_LAUNCH records the expression's
+// text, and the census and the profiles key on that of the forward and the ancestral step). BIG: the five may use up
+// to kTailSmemMax of dynamic shared memory; the attribute is set once. PXB: the pixels of a block. The modes that end
+// in statistics are followed by their finalize launch, and are refused where a block would straddle two images (an
+// image is not a whole number of blocks).
+#define ITSD_RETURN_TAIL_LAUNCH(PLAIN, FAMILY, BIG, PXB, grid, block, sm, s, a)                                      \
+  do {                                                                                                               \
+    const auto member = [](auto epi) -> TailKernel {                                                                 \
+      constexpr int E = decltype(epi)::value;                                                                        \
+      return FAMILY;                                                                                                 \
+    };                                                                                                               \
+    const TailKernel kern[] = {member(TailEpi<0>{}), member(TailEpi<1>{}), member(TailEpi<2>{}),                     \
+                               member(TailEpi<3>{}), member(TailEpi<4>{})};                                          \
+    static bool attr = !(BIG);                                                                                       \
+    if (!attr) {                                                                                                     \
+      for (const TailKernel f : kern) {                                                                              \
+        hipError_t e = hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize,               \
+                                           (int)kTailSmemMax);                                                       \
+        if (e != hipSuccess) return e;                                                                               \
+      }                                                                                                              \
+      attr = true;                                                                                                   \
+    }                                                                                                                \
+    const int epi = tail_epi((a).step_mode), nst = tail_stats((a).step_mode);                                        \
+    if (nst && ((a).n < 1 || ((a).H * (a).W) % (PXB))) return hipErrorInvalidValue;                                  \
+    if (epi == 0) ITSD_LAUNCH(PLAIN, grid, block, sm, s, a);                                                         \
+    else ITSD_LAUNCH(kern[epi], grid, block, sm, s, a);                                                              \
+    if (nst) {                                                                                                       \
+      const bool traced = (a).step_mode == kTailX0StepMom;                                                           \
+      ITSD_LAUNCH(tail_stats_finalize_kernel, dim3((nst * (a).n + 63) / 64), dim3(64), 0, s,                         \
+                  traced ? (a).tpart : (a).vpart, (a).H * (a).W / (PXB), (a).n, nst, traced ? (a).tsel : nullptr,    \
+                  traced ? (a).trace : (a).vsse, traced ? (a).trace_rows : 1, traced ? (a).trace_stride : (a).n);    \
+    }                                                                                                                \
+    return hipGetLastError();                                                                                        \
   } while (0)
 
 hipError_t launch_tail_mfma(const TailArgs& a, hipStream_t s) {
   if (!a.coef || !a.wmf || !tail_mfma_ok(a.H, a.W, a.C) || !tail_x0_ok(a)) return hipErrorInvalidValue;
   const dim3 grid(a.n * (a.H / (128 / a.W)));
   const size_t sm = tail_mfma_smem_px(128, a.H, a.W, a.C);
-  ITSD_RETURN_TAIL_LAUNCH((tail_mfma_kernel<128, 512>), (tail_mfma_kernel<128, 512, 1>), (tail_mfma_kernel<128, 512, 2>),
-                          (tail_mfma_kernel<128, 512, 3>), (tail_mfma_kernel<128, 512, 4>), true, grid, dim3(512), sm, s,
-                          a);
+  ITSD_RETURN_TAIL_LAUNCH((tail_mfma_kernel<128, 512>), (tail_mfma_kernel<128, 512, E>), true, 128, grid, dim3(512), sm,
+                          s, a);
 }
 
 template <typename T>
@@ -2131,17 +2046,14 @@ hipError_t launch_tail(const TailArgs& a, hipStream_t s) {
     const size_t sm = 27 * a.C * 4 + (size_t)(64 / a.W + 2) * (a.W + 2) * (a.C * sizeof(T) + 16) + 2 * 4 * 64 * 3 * 4;
     if (sm > kTailSmemMax) return hipErrorInvalidValue;
     const dim3 grid(a.n * (a.H / (64 / a.W)));
-    ITSD_RETURN_TAIL_LAUNCH(tail2_kernel<T>, (tail2_kernel<T, 1>), (tail2_kernel<T, 2>), (tail2_kernel<T, 3>),
-                            (tail2_kernel<T, 4>), true, grid, dim3(256), sm, s, a);
+    ITSD_RETURN_TAIL_LAUNCH(tail2_kernel<T>, (tail2_kernel<T, E>), true, 64, grid, dim3(256), sm, s, a);
   }
   const long long total = (long long)a.n * a.H * a.W;
   const dim3 grid((unsigned)((total + 255) / 256));
-  if ((a.step_mode == 4 || a.step_mode == 5) && (a.H * a.W) % 256)
-    return hipErrorInvalidValue;  // (a block of 256 pixels would straddle)
-  ITSD_RETURN_TAIL_LAUNCH(tail_kernel<T>, (tail_kernel<T, 1>), (tail_kernel<T, 2>), (tail_kernel<T, 3>),
-                          (tail_kernel<T, 4>), false, grid, dim3(256), 27 * a.C * sizeof(float), s, a);
+  ITSD_RETURN_TAIL_LAUNCH(tail_kernel<T>, (tail_kernel<T, E>), false, 256, grid, dim3(256), 27 * a.C * sizeof(float), s,
+                          a);
 }
-// Whether the per-block sums of step_mode 4 / 5 are refused at this geometry: launch_tail (not the MFMA tail, whose
+// Whether the per-block statistics of kTailSse / kTailX0StepMom are refused at this geometry: launch_tail (not the MFMA tail, whose
 // blocks are whole rows of one image) falls to tail_kernel and its 256-pixel blocks would straddle two images.
 bool tail_block_straddles(int H, int W, int C) {
   const bool tiled = W <= 64 && 64 % W == 0 && H % (64 / W) == 0 && C % 32 == 0;

@@ -13,9 +13,9 @@ off by at most L u sum|x0| to first order, and one more u covers the second-orde
     |S - S_ref| <= (1 + L) u sum|x0|
 For Q each square x0 x0 rounds once (u on every term) before its L additions of non-negative terms:
     |Q - Q_ref| <= (2 + L) u Q_ref
-L is the longest chain of fp32 additions an element passes through, the sse epilogue's tree (tail_mom_block is
-tail_sse_block on four values): the thread's own items, the 6-level lane butterfly, the wave partials
-in wave order:
+L is the longest chain of fp32 additions an element passes through, the sse epilogue's tree (both modes end in
+tail_block_stats, on two and on four values): the thread's own items, the 6-level lane butterfly, the
+wave partials in wave order:
     tail2_kernel       1 item a thread (0 + x0 is exact)       0 + 6 + 3 (4 waves)  =  9
     tail_kernel        3 items a thread                        2 + 6 + 3 (4 waves)  = 11
     tail_mfma_kernel   1 item a thread                         0 + 6 + 7 (8 waves)  = 13
