@@ -20,6 +20,8 @@
  *                                   run at timestep tau[k], stepped by DDIM(eta) written through the x_0 estimate
  *                                   (optionally clipped, Ho et al.'s clip_denoised). Opt-in: itsd_set_schedule's
  *                                   ancestral form stays the default and the parity contract
+ *   itsd_set_schedule_x0_2m      <- (no reference counterpart) the same K rows stepped second order: DPM-Solver++(2M)
+ *                                   in data prediction, with the previous row's x_0 estimate kept by the library
  *   itsd_sampler_predict_x0      <- (no reference counterpart) the x_0 estimate of a half-denoised state, what a
  *                                   verifier can score mid-trajectory: the branching PathSearch its docstring
  *                                   describes (search/search_algorithm.py:238-250; its code, :307-312, is a placeholder)
@@ -91,6 +93,7 @@ enum { ITSD_VERIFY_ORACLE = 0, ITSD_VERIFY_SELFSUP = 1, ITSD_VERIFY_AESTHETIC = 
 #define ITSD_RUN_GRAPH 1u   /* capture one denoising step in a hipGraph and replay it */
 #define ITSD_RUN_CLIP 2u    /* clip(x, -1, 1) after the last step (Diffusion.py:102) */
 #define ITSD_RUN_SYNC 4u    /* synchronise at the end and report ITSD_ERR_NAN */
+#define ITSD_RUN_CONTINUE 8u /* 2M schedule only: the step at t_begin reads the x_0 the previous run left (below) */
 
 typedef struct itsd_unet itsd_unet;
 
@@ -163,6 +166,28 @@ typedef struct {
  * strictly increasing, clip_x0 outside {0, 1}, a null handle, CFG with tau[K-1] >= the embedding table's rows. */
 int itsd_set_schedule_x0(itsd_unet* u, const itsd_x0_schedule* schedule);
 
+/* The 2M schedule: DPM-Solver++(2M) in data prediction on the rows of an x0-form schedule. Everything
+ * itsd_set_schedule_x0 does, plus a sixth HOST table cp[K] and a library-owned history hist[max_batch][3][H][W] fp32
+ * (allocated at the first such call on the handle, filled by itsd_unet_poison like every buffer); "sched_form" = 2. The
+ * three schedule calls replace one another. Row k steps, in fp32 without contraction,
+ *     x0 = a0[k] x - b0[k] eps,  clipped to [-1, 1] iff clip_x0
+ *     cp[k] != 0:  x0p = (k == restart row) ? x0 : hist ;   m = ((c0[k] x0) + (cp[k] x0p)) + (cx[k] x)
+ *     cp[k] == 0:  m = (c0[k] x0) + (cx[k] x)               (hist is not read)
+ *     hist = x0 ;  x' = sg[k] != 0 ? m + sg[k] z : m
+ * With lambda_k = ln(abar_k / (1 - abar_k)) / 2, h = lambda_{k-1} - lambda_k, r = (lambda_k - lambda_{k+1}) / h and
+ * c0d the eta = 0 value of itsd_set_schedule_x0's c0, the caller passes c0[k] = c0d[k] (1 + 1/(2r)) and
+ * cp[k] = -c0d[k] / (2r) for 1 <= k <= K - 2; rows K - 1 (no predecessor) and 0 (an infinite last lambda gap) keep c0d
+ * and cp = 0: they are first order, and row 0 stays (1, 0, 0). Under CFG hist holds the guided x0 of the n candidates.
+ * The restart row: itsd_sampler_run without ITSD_RUN_CONTINUE treats its first step as having no history (the step
+ * uses its own x0 for x0p); with the flag the step at t_begin reads what the previous run on this handle left. The
+ * handle remembers the row whose x0 hist holds and for how many images (a run sets them to its t_end and n; installing
+ * any schedule forgets them), and the flag is refused unless they are t_begin + 1 and n. The restart row is a device
+ * run parameter: one captured step graph serves restarted and continued runs.
+ * itsd_sampler_predict_x0, itsd_verify_denoise and itsd_unet_forward neither read nor write hist.
+ * ITSD_ERR_INVALID with a message naming this function, before any HIP call: everything itsd_set_schedule_x0 refuses,
+ * a null cp, a cp[k] that is not finite, cp[K-1] != 0. */
+int itsd_set_schedule_x0_2m(itsd_unet* u, const itsd_x0_schedule* schedule, const float* cp);
+
 /* Run steps t_begin..t_end (inclusive, descending) of the ancestral sampler in
  * place on x[n,3,H,W]. With ITSD_RUN_GRAPH one denoising step is captured per
  * (n, x, labels, noise, option state) and replayed: seed, noise_offset and the clip
@@ -170,12 +195,15 @@ int itsd_set_schedule_x0(itsd_unet* u, const itsd_x0_schedule* schedule);
  * (seed, step, noise_offset + element); otherwise noise is [T][n][3][H][W] fp32 and
  * step t uses noise[t] (t >= 1; the reference draws no noise at t = 0). labels: CFG only.
  * Under an x0-form schedule (itsd_set_schedule_x0) the same call walks rows with that schedule's step; a graph
- * captured under one form is never replayed under the other (the form is part of the cache key). */
+ * captured under one form is never replayed under another (the form is part of the cache key).
+ * ITSD_RUN_CONTINUE (itsd_set_schedule_x0_2m) is refused with ITSD_ERR_INVALID before any launch under the other two
+ * forms, at t_begin == K - 1, and when the history does not hold row t_begin + 1 of n images. */
 int itsd_sampler_run(itsd_unet* u, float* x, const int32_t* labels, int n, int t_begin, int t_end,
                      uint64_t seed, int64_t noise_offset, const float* noise, uint32_t flags, void* stream);
 
 /* Attach (trace != NULL) or detach a score trace. trace: device fp64 [rows][stride][4], caller-owned,
- * 32-byte aligned; rows must equal T_sched of the installed x0-form schedule, stride >= the n of every run.
+ * 32-byte aligned; rows must equal T_sched of the installed x0-form schedule (either form: under the 2M schedule the
+ * moments are those of the row's own x0, not of the multistep combination), stride >= the n of every run.
  * While attached, step k of itsd_sampler_run on images i < n writes
  * trace[k][i] = (sum x0, sum x0^2, min x0, max x0) over the image's 3 H W elements,
  * x0 the estimate that step used (clipped iff clip_x0); rows not run and images >= n are not written.
@@ -346,7 +374,7 @@ int itsd_set_option(const char* key, int value);
 
 /* Introspection of a handle (no device work): "graph_captures" (step graphs captured and
  * instantiated so far; a search replays one graph across all its rounds), "max_batch",
- * "T_sched" (timesteps, or the rows K of an x0-form schedule), "sched_form" (0 ancestral, 1 x0-form), "trace" (1 while a score trace is attached), "ws_bytes"
+ * "T_sched" (timesteps, or the rows K of an x0-form schedule), "sched_form" (0 ancestral, 1 x0-form, 2 the 2M x0-form), "trace" (1 while a score trace is attached), "ws_bytes"
  * (activation arena), "ops" (program length); and, synchronising the
  * handle's stream, "status" = the in-kernel hand-off status word of the last forward / sampler run
  * (0 ok; bit 0: attn_block_split_kernel's wait exhausted its bound, bit 1: conv3x3_gn_p5_kernel's shared split-K

@@ -218,9 +218,14 @@ struct itsd_unet {
   float* temb_table = nullptr;  // [T_sched][sumC]
   // x0-form schedule (itsd_set_schedule_x0): sched_form 1, T_sched = its rows K, temb_table row k = timestep tau[k]'s,
   // xrow = one allocation [5][K] (a0 | b0 | c0 | cx | sg); the three ancestral tables are then null, and the reverse
+  // 2M schedule (itsd_set_schedule_x0_2m): sched_form 2, xrow = [6][K] with cp last; x0_hist = the previous row's x0
+  // [max_batch][3][H][W] fp32, allocated at the first such call and kept; hist_row / hist_n = the row whose x0 it holds
+  // and for how many images (-1 / 0: nothing a continued run may read)
   int sched_form = 0;
   float* xrow = nullptr;
   int clip_x0 = 0;
+  float* x0_hist = nullptr;
+  int hist_row = -1, hist_n = 0;
   float guide_w = 0.f, guide_w1 = 1.f;
   int* d_t = nullptr;
   int* d_nan = nullptr;
@@ -1349,6 +1354,8 @@ void drop_schedule(itsd_unet* u) {
   u->T_sched = 0;
   u->sched_form = 0;
   u->clip_x0 = 0;
+  u->hist_row = -1;
+  u->hist_n = 0;
 }
 
 int check_batch(itsd_unet* u, int n) {
@@ -1696,7 +1703,7 @@ int itsd_unet_destroy(itsd_unet* u) {
   clear_graphs(u);
   hipFree(u->wdev); hipFree(u->ws); hipFree(u->emb_buf); hipFree(u->h1_buf); hipFree(u->te_buf);
   hipFree(u->proj_buf); hipFree(u->cemb_table); hipFree(u->coeff1); hipFree(u->coeff2); hipFree(u->sqrt_var);
-  hipFree(u->xrow); hipFree(u->temb_table); hipFree(u->d_t); hipFree(u->d_nan); hipFree(u->d_run); hipFree(u->x_state); hipFree(u->lab_state); hipFree(u->zero_page);
+  hipFree(u->xrow); hipFree(u->temb_table); hipFree(u->d_t); hipFree(u->d_nan); hipFree(u->d_run); hipFree(u->x0_hist); hipFree(u->x_state); hipFree(u->lab_state); hipFree(u->zero_page);
   hipFree(u->splitk_ws);
   hipFree(u->tickets);
   hipFree(u->attn_sync);
@@ -1762,29 +1769,43 @@ int itsd_set_schedule(itsd_unet* u, int T, const float* coeff1, const float* coe
   return ITSD_OK;
 }
 
-// The x0-form schedule: K rows, row k run at timestep tau[k]. The time-embedding table is built for tau (temb_rows with
+// The x0-form schedules: K rows, row k run at timestep tau[k]. The time-embedding table is built for tau (temb_rows with
 // a device copy of it), so everything downstream -- the step program, itsd_sampler_predict_x0 -- indexes by row.
-int itsd_set_schedule_x0(itsd_unet* u, const itsd_x0_schedule* sc) {
-  if (!sc) return fail(ITSD_ERR_INVALID, "itsd_set_schedule_x0: null schedule");
-  if (!sc->tau || !sc->a0 || !sc->b0 || !sc->c0 || !sc->cx || !sc->sg)
-    return fail(ITSD_ERR_INVALID, "itsd_set_schedule_x0: null table");
+// cp: null for itsd_set_schedule_x0 (form 1); the sixth table of itsd_set_schedule_x0_2m (form 2), which also owns the
+// x0 history. fn names the entry point in every refusal; all of them come before the first HIP call.
+static int install_x0_schedule(itsd_unet* u, const itsd_x0_schedule* sc, const float* cp, bool two_m, const char* fn) {
+  const std::string who = std::string(fn) + ": ";
+  if (!sc) return fail(ITSD_ERR_INVALID, who + "null schedule");
+  if (!sc->tau || !sc->a0 || !sc->b0 || !sc->c0 || !sc->cx || !sc->sg || (two_m && !cp))
+    return fail(ITSD_ERR_INVALID, who + "null table");
   const int K = sc->K;
-  if (K < 1) return fail(ITSD_ERR_INVALID, "itsd_set_schedule_x0: K = " + std::to_string(K) + " < 1");
+  if (K < 1) return fail(ITSD_ERR_INVALID, who + "K = " + std::to_string(K) + " < 1");
   for (int k = 0; k < K; ++k)
     if (sc->tau[k] < 0 || (k && sc->tau[k] <= sc->tau[k - 1]))
-      return fail(ITSD_ERR_INVALID, "itsd_set_schedule_x0: tau[" + std::to_string(k) + "] = " +
-                                        std::to_string(sc->tau[k]) + ": timesteps must be >= 0 and strictly increasing");
+      return fail(ITSD_ERR_INVALID, who + "tau[" + std::to_string(k) + "] = " + std::to_string(sc->tau[k]) +
+                                        ": timesteps must be >= 0 and strictly increasing");
   if (sc->clip_x0 != 0 && sc->clip_x0 != 1)
-    return fail(ITSD_ERR_INVALID, "itsd_set_schedule_x0: clip_x0 = " + std::to_string(sc->clip_x0) + " is neither 0 nor 1");
-  if (!u) return fail(ITSD_ERR_INVALID, "itsd_set_schedule_x0: null handle");
+    return fail(ITSD_ERR_INVALID, who + "clip_x0 = " + std::to_string(sc->clip_x0) + " is neither 0 nor 1");
+  if (two_m) {
+    for (int k = 0; k < K; ++k)
+      if (!std::isfinite(cp[k]))
+        return fail(ITSD_ERR_INVALID, who + "cp[" + std::to_string(k) + "] is not finite");
+    if (cp[K - 1] != 0.f)
+      return fail(ITSD_ERR_INVALID, who + "cp[K - 1] = " + std::to_string(cp[K - 1]) +
+                                        " != 0: the top row has no predecessor");
+  }
+  if (!u) return fail(ITSD_ERR_INVALID, who + "null handle");
   if (u->cfg && sc->tau[K - 1] >= u->d.T)
     return fail(ITSD_ERR_INVALID, "CFG time-embedding table has " + std::to_string(u->d.T) + " rows <= timestep " +
                                       std::to_string(sc->tau[K - 1]));
   HIPCHK(hipSetDevice(u->device));
   drop_schedule(u);
-  HIPCHK(hipMalloc(&u->xrow, (size_t)5 * K * 4));
-  const float* rows[5] = {sc->a0, sc->b0, sc->c0, sc->cx, sc->sg};
-  for (int i = 0; i < 5; ++i) HIPCHK(hipMemcpy(u->xrow + (size_t)i * K, rows[i], (size_t)K * 4, hipMemcpyHostToDevice));
+  const int ntab = two_m ? 6 : 5;
+  HIPCHK(hipMalloc(&u->xrow, (size_t)ntab * K * 4));
+  const float* rows[6] = {sc->a0, sc->b0, sc->c0, sc->cx, sc->sg, cp};
+  for (int i = 0; i < ntab; ++i)
+    HIPCHK(hipMemcpy(u->xrow + (size_t)i * K, rows[i], (size_t)K * 4, hipMemcpyHostToDevice));
+  if (two_m && !u->x0_hist) HIPCHK(hipMalloc(&u->x0_hist, vd_xt_bytes(u)));
   HIPCHK(hipMalloc(&u->temb_table, (size_t)K * u->sumC * 4));
   CHK(alloc_rows(u, K));
   int* d_tau = nullptr;
@@ -1796,11 +1817,19 @@ int itsd_set_schedule_x0(itsd_unet* u, const itsd_x0_schedule* sc) {
   hipFree(d_tau);
   if (rc != ITSD_OK) return rc;
   u->T_sched = K;
-  u->sched_form = 1;
+  u->sched_form = two_m ? 2 : 1;
   u->clip_x0 = sc->clip_x0;
   u->guide_w = sc->w;
   u->guide_w1 = (float)(1.0 + (double)sc->w);
   return ITSD_OK;
+}
+
+int itsd_set_schedule_x0(itsd_unet* u, const itsd_x0_schedule* sc) {
+  return install_x0_schedule(u, sc, nullptr, false, "itsd_set_schedule_x0");
+}
+
+int itsd_set_schedule_x0_2m(itsd_unet* u, const itsd_x0_schedule* sc, const float* cp) {
+  return install_x0_schedule(u, sc, cp, true, "itsd_set_schedule_x0_2m");
 }
 
 int itsd_sampler_run(itsd_unet* u, float* x, const int32_t* labels, int n, int t_begin, int t_end, uint64_t seed,
@@ -1810,6 +1839,21 @@ int itsd_sampler_run(itsd_unet* u, float* x, const int32_t* labels, int n, int t
   if (u->cfg && !labels) return fail(ITSD_ERR_INVALID, "CFG sampler needs labels");
   CHK(check_batch(u, n));
   if (t_begin >= u->T_sched || t_end < 0 || t_end > t_begin) return fail(ITSD_ERR_INVALID, "bad step range");
+  if (flags & ITSD_RUN_CONTINUE) {  // (host state only: refused before anything is queued)
+    if (u->sched_form != 2)
+      return fail(ITSD_ERR_INVALID, "itsd_sampler_run: ITSD_RUN_CONTINUE needs a 2M schedule (itsd_set_schedule_x0_2m): "
+                                    "the other forms keep no x0 history");
+    if (t_begin == u->T_sched - 1)
+      return fail(ITSD_ERR_INVALID, "itsd_sampler_run: ITSD_RUN_CONTINUE at the top row " + std::to_string(t_begin) +
+                                        ", which has no predecessor");
+    if (u->hist_row != t_begin + 1)
+      return fail(ITSD_ERR_INVALID, "itsd_sampler_run: ITSD_RUN_CONTINUE at row " + std::to_string(t_begin) +
+                                        " needs the x0 of row " + std::to_string(t_begin + 1) + "; the history holds " +
+                                        (u->hist_row < 0 ? std::string("none") : "row " + std::to_string(u->hist_row)));
+    if (u->hist_n != n)
+      return fail(ITSD_ERR_INVALID, "itsd_sampler_run: ITSD_RUN_CONTINUE with n = " + std::to_string(n) +
+                                        ", the history holds " + std::to_string(u->hist_n) + " images");
+  }
   if (u->trace) {  // (attached under this x0-form schedule: itsd_sampler_set_trace, drop_schedule)
     if (n > u->trace_stride)
       return fail(ITSD_ERR_INVALID, "itsd_sampler_run: batch " + std::to_string(n) + " > the attached trace's stride " +
@@ -1829,13 +1873,19 @@ int itsd_sampler_run(itsd_unet* u, float* x, const int32_t* labels, int n, int t
 
   RunCtx c = step_ctx(u, n, u->x_state, labels ? u->lab_state : nullptr);
   TailArgs& t = c.tail;
-  t.step_mode = u->sched_form ? kTailX0Step : kTailStep; t.tsel = u->d_t;
+  const bool two_m = u->sched_form == 2;
+  t.step_mode = two_m ? kTailX0Step2M : u->sched_form ? kTailX0Step : kTailStep; t.tsel = u->d_t;
   t.coeff1 = u->coeff1; t.coeff2 = u->coeff2; t.sqrt_var = u->sqrt_var;
   if (u->sched_form) {  // rows, not timesteps: d_t, the Philox stream id and the injected-noise index are the row
     for (int i = 0; i < 5; ++i) t.xrow[i] = u->xrow + (size_t)i * u->T_sched;
     t.clip_x0 = u->clip_x0;
+    if (two_m) {  // (in the storage of the two ancestral pointers, null under this form)
+      t.xcp = u->xrow + (size_t)5 * u->T_sched;
+      t.hist = u->x0_hist;
+      u->hist_row = -1;  // (until the run is queued whole)
+    }
     if (u->trace) {
-      t.step_mode = kTailX0StepMom;
+      t.step_mode = two_m ? kTailX0Step2MMom : kTailX0StepMom;
       t.tpart = u->tr_part; t.trace = u->trace; t.trace_rows = u->trace_rows; t.trace_stride = u->trace_stride;
     }
   }
@@ -1843,6 +1893,8 @@ int itsd_sampler_run(itsd_unet* u, float* x, const int32_t* labels, int n, int t
 
   RunParams rp{};
   rp.seed = seed; rp.noise_offset = noise_offset; rp.clip_at = clip_at;
+  // a device parameter, so one captured step graph serves restarted and continued runs (read by the 2M modes only)
+  rp.restart_at = (flags & ITSD_RUN_CONTINUE) ? -1 : t_begin;
   HIPCHK(launch_run_begin(u->d_t, t_begin, u->d_nan, u->d_run, rp, s));
   const int steps = t_begin - t_end + 1;
   if (flags & ITSD_RUN_GRAPH) {
@@ -1858,6 +1910,10 @@ int itsd_sampler_run(itsd_unet* u, float* x, const int32_t* labels, int n, int t
   }
   HIPCHK(hipMemcpyAsync(x, u->x_state, xbytes, hipMemcpyDeviceToDevice, s));
   CHK(leave_stream(u, cs));
+  if (two_m) {  // what this run leaves, for a later ITSD_RUN_CONTINUE
+    u->hist_row = t_end;
+    u->hist_n = n;
+  }
   if (flags & ITSD_RUN_SYNC) {
     HIPCHK(hipStreamSynchronize(s));
     int flag[2] = {0, 0};
@@ -1876,7 +1932,7 @@ int itsd_sampler_set_trace(itsd_unet* u, double* trace, int rows, int stride) {
     return ITSD_OK;
   }
   if (!u->T_sched || !u->sched_form)
-    return fail(ITSD_ERR_INVALID, "itsd_sampler_set_trace: no x0-form schedule installed (itsd_set_schedule_x0; the "
+    return fail(ITSD_ERR_INVALID, "itsd_sampler_set_trace: no x0-form schedule installed (itsd_set_schedule_x0 / _2m; the "
                                   "ancestral form has no x0 rows)");
   if (rows != u->T_sched)
     return fail(ITSD_ERR_INVALID, "itsd_sampler_set_trace: rows = " + std::to_string(rows) + " != T_sched = " +
@@ -2316,6 +2372,9 @@ int itsd_unet_poison(itsd_unet* u, void* stream) {
   if (u->vd_part) HIPCHK(hipMemsetAsync(u->vd_part, 0xFF, vd_part_bytes(u), u->stream));
   // the traced step's per-block partials (once they exist): the tail stores every one its finalize launch reads
   if (u->tr_part) HIPCHK(hipMemsetAsync(u->tr_part, 0xFF, tr_part_bytes(u), u->stream));
+  // the 2M step's x0 history (once it exists): a restarted run reads none of it, a continued one what the run before
+  // it stored (the host's hist_row / hist_n stay: poisoning is a test of that claim, not an invalidation)
+  if (u->x0_hist) HIPCHK(hipMemsetAsync(u->x0_hist, 0xFF, vd_xt_bytes(u), u->stream));
   u->last_forward_n = 0;  // (the tail input is gone: itsd_unet_representation refuses until the next forward)
   return leave_stream(u, cs);
 }

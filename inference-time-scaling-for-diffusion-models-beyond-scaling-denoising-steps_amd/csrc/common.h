@@ -2,6 +2,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 namespace itsd {
@@ -384,10 +385,11 @@ struct RunParams {
   unsigned long long seed;  // Philox key of the per-step noise z
   long long noise_offset;   // Philox element offset (global candidate index * per-candidate elements)
   int clip_at;              // clip when t == clip_at (-1: never)
-  int pad_;
+  int restart_at;           // the 2M step at row t == restart_at has no history: it uses its own x0 twice (-1: none)
 };
+static_assert(sizeof(RunParams) == 24, "RunParams is the argument of run_begin_kernel and a device block: fixed");
 
-// The six ways the tail ends (TailArgs::step_mode; kernels.hip's header comment describes each). The values are the
+// The eight ways the tail ends (TailArgs::step_mode; kernels.hip's header comment describes each). The values are the
 // ABI of TailArgs and stay.
 enum TailMode : int {
   kTailEps = 0,        // write eps NCHW (the forward API)
@@ -396,6 +398,8 @@ enum TailMode : int {
   kTailX0Step = 3,     // the x0-form update of x in place (rows of xrow)
   kTailSse = 4,        // the denoising-error sums
   kTailX0StepMom = 5,  // kTailX0Step plus the x0 moments of every image
+  kTailX0Step2M = 6,     // the second-order multistep x0-form update (the previous row's x0 from TailArgs::hist)
+  kTailX0Step2MMom = 7,  // kTailX0Step2M plus the x0 moments of every image
 };
 // EPI, the tail kernels' template parameter: eps and step share instantiation 0 (a.step_mode tells them apart at
 // run time); every other mode has its own.
@@ -405,11 +409,16 @@ constexpr TailMode tail_epi_mode(int epi, bool step) { return epi ? TailMode(epi
 // what a mode does
 constexpr bool tail_reads_x(int mode) { return mode != kTailEps && mode != kTailSse; }
 constexpr bool tail_loads_row(int mode) {  // row *tsel of the schedule tables and the run's parameters
-  return mode == kTailStep || mode == kTailX0Step || mode == kTailX0StepMom;
+  return mode == kTailStep || mode == kTailX0Step || mode == kTailX0StepMom || mode == kTailX0Step2M ||
+         mode == kTailX0Step2MMom;
 }
-constexpr bool tail_x0_form(int mode) { return mode == kTailX0Step || mode == kTailX0StepMom; }
+constexpr bool tail_x0_form(int mode) {
+  return mode == kTailX0Step || mode == kTailX0StepMom || mode == kTailX0Step2M || mode == kTailX0Step2MMom;
+}
+constexpr bool tail_2m(int mode) { return mode == kTailX0Step2M || mode == kTailX0Step2MMom; }  // reads cp and hist
+constexpr bool tail_traced(int mode) { return mode == kTailX0StepMom || mode == kTailX0Step2MMom; }
 // the block statistics it ends in (tail_block_stats: 2 sums; 2 sums, min, max), 0 where it ends in none
-constexpr int tail_stats(int mode) { return mode == kTailSse ? 2 : mode == kTailX0StepMom ? 4 : 0; }
+constexpr int tail_stats(int mode) { return mode == kTailSse ? 2 : tail_traced(mode) ? 4 : 0; }
 
 struct TailArgs {
   const void* g;        // NHWC [nb][H][W][C] : silu(gn(h))
@@ -424,7 +433,11 @@ struct TailArgs {
   float* eps_out;       // NCHW [n][3][H][W]
   float* x;             // NCHW [n][3][H][W]
   const int* tsel;      // current step t (device)
-  const float* coeff1; const float* coeff2; const float* sqrt_var;
+  // (the ancestral tables; the x0-form modes never read them, and the 2M modes keep their two operands in the storage
+  // of the first two: xcp, the sixth row table cp[K], and hist, the previous row's x0 NCHW fp32 [n][3][H][W])
+  union { const float* coeff1; const float* xcp; };
+  union { const float* coeff2; float* hist; };
+  const float* sqrt_var;
   const float* noise;   // [T][n][3][H][W] or null
   const RunParams* run; // seed / noise offset / clip step of this run (device)
   int* nan_flag;
@@ -461,7 +474,17 @@ struct TailArgs {
   int trace_stride;
   union { float* vpart; float* tpart; };
   union { double* vsse; double* trace; };
+  // kTailX0Step2M / kTailX0Step2MMom (itsd_sampler_run under itsd_set_schedule_x0_2m): the x0 step with the multistep
+  // correction  m = ((c0*x0) + (cp*x0p)) + (cx*x),  cp = xcp[*tsel], x0p = hist[o] (this row's own x0 where
+  // *tsel == RunParams::restart_at); a row with cp == 0 is kTailX0Step's expression and does not read hist. Every
+  // row stores its x0 to hist[o]. The Mom form adds this row's x0 (not the combination) to the moments.
 };
+static_assert(sizeof(TailArgs) == 240, "TailArgs is the tail kernels' argument block: a larger one changed the "
+                                       "register allocation of the existing instantiations (DESIGN section 13)");
+static_assert(offsetof(TailArgs, xcp) == offsetof(TailArgs, coeff1) && offsetof(TailArgs, coeff1) == 80 &&
+                  offsetof(TailArgs, hist) == offsetof(TailArgs, coeff2) && offsetof(TailArgs, coeff2) == 88 &&
+                  offsetof(TailArgs, sqrt_var) == 96,
+              "the 2M operands overlay the ancestral tables");
 
 constexpr int kBranchChunk = 256;  // parent-table rows a branch_kernel launch carries in its arguments (1 KiB)
 

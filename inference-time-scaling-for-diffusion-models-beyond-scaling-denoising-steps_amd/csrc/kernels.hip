@@ -1419,7 +1419,7 @@ __device__ __forceinline__ float philox_normal(unsigned long long seed, unsigned
 // tail = GN -> Swish -> Conv2d(C, 3, 3, padding=1) (Model.py:252-256, 282). The GN+Swish
 // output g is produced by groupnorm_kernel (tail_mfma_kernel applies it itself); the three kernels below do the
 // 3-output conv per pixel and hand each output element's unguided eps pair to tail_item, the one epilogue of all three,
-// which ends in one of six ways (TailArgs::step_mode, a TailMode of common.h):
+// which ends in one of eight ways (TailArgs::step_mode, a TailMode of common.h):
 //   eps  (kTailEps, the forward API)  eps_out = eps
 //   step (kTailStep)  the ancestral update of Diffusion.py:67-71,96-100 in place on x:
 //          mean = coeff1[t]*x - coeff2[t]*eps ;  x = mean + sqrt(var[t]) * z  (z = 0 at t = 0; injected or Philox),
@@ -1452,9 +1452,22 @@ __device__ __forceinline__ float philox_normal(unsigned long long seed, unsigned
 //          max), reduced by tail_block_stats (the sse sums' tree, on four values) into tpart[blockIdx.x][4];
 //          tail_stats_finalize_kernel folds each image's blocks in block order in fp64 into row *tsel of the caller's
 //          trace. No atomics.
+//   2M step (kTailX0Step2M, its own instantiation)  DPM-Solver++(2M) in data prediction: the x0 step with the previous
+//          row's x0 in the combination, in place on x and on the history hist (NCHW fp32 [n][3][H][W], the guided x0
+//          of the n candidates). Row k = *tsel of the five xrow tables and of a sixth, cp = xcp[k]:
+//          x0 = a0*x - b0*eps, clipped iff clip_x0 ;
+//          cp != 0:  x0p = (k == RunParams::restart_at) ? x0 : hist[o] ;  m = ((c0*x0) + (cp*x0p)) + (cx*x)
+//          cp == 0:  m = (c0*x0) + (cx*x)   (the x0 step's expression; hist[o] is not read)
+//          hist[o] = x0 ;  x = sg != 0 ? m + sg*z : m   (z, NaN test, clip_at clip and flag as the x0 step; no
+//          contraction). cp != 0 and k == restart_at are wave-uniform (one row a launch); hist[o] is read and then
+//          written by the one thread that owns element o. The x0 step's instantiations are not touched: xcp and hist
+//          share the storage of the ancestral tables' pointers, which no x0-form mode reads.
+//   2M step + moments (kTailX0Step2MMom, its own instantiation)  the 2M step, bit-identical x and hist, and the
+//          moments of this row's own x0 (not of the combination) as in the x0 step + moments.
 // EPI, the kernels' template parameter, names the instantiation (tail_epi of common.h): 0 eps / step, 1 x0, 2 x0 step,
-// 3 sse, 4 x0 step + moments. Each kernel ends in one loop over its output items, which calls tail_item, and one call
-// of tail_block_stats, which every thread of the block reaches and which is empty where the mode ends in no statistics.
+// 3 sse, 4 x0 step + moments, 5 2M step, 6 2M step + moments. Each kernel ends in one loop over its output items, which
+// calls tail_item, and one call of tail_block_stats, which every thread of the block reaches and which is empty where
+// the mode ends in no statistics.
 __device__ __forceinline__ float tail_x0(float a0, float b0, float xv, float e) {
 #pragma clang fp contract(off)
   const float v = a0 * xv - b0 * e;
@@ -1471,7 +1484,8 @@ template <int EPI> constexpr TailMode kTailMode = tail_epi_mode(EPI, false);
 
 // The step's scalars: row t of the schedule tables and the run's parameters. Loaded in the step modes only (the
 // x0 step: c1, c2, sv hold the row's c0, cx, sg, and a0, b0 its x_0 coefficients); the other modes read none of
-// them.
+// them. The 2M modes carry two more, in a type of their own (TailStepOf): a larger TailStep reordered two scalar loads
+// of the ancestral tail_mfma_kernel.
 struct TailStep {
   int t = 0;
   float c1 = 0.f, c2 = 0.f, sv = 0.f;
@@ -1480,9 +1494,14 @@ struct TailStep {
   int clip_at = -1;
   float a0 = 0.f, b0 = 0.f;
 };
+struct TailStep2M : TailStep {
+  float cp = 0.f;       // the row's weight of the previous row's x0
+  int restart_at = -1;  // RunParams::restart_at
+};
+template <int EPI> using TailStepOf = std::conditional_t<tail_2m(kTailMode<EPI>), TailStep2M, TailStep>;
 template <int EPI>
-__device__ __forceinline__ TailStep tail_step_load(const TailArgs& a) {
-  TailStep s;
+__device__ __forceinline__ TailStepOf<EPI> tail_step_load(const TailArgs& a) {
+  TailStepOf<EPI> s;
   if (tail_loads_row(tail_mode<EPI>(a))) {
     s.t = *a.tsel;
     s.seed = a.run->seed;
@@ -1494,6 +1513,10 @@ __device__ __forceinline__ TailStep tail_step_load(const TailArgs& a) {
       s.c1 = a.xrow[2][s.t];
       s.c2 = a.xrow[3][s.t];
       s.sv = a.xrow[4][s.t];
+      if constexpr (tail_2m(kTailMode<EPI>)) {
+        s.cp = a.xcp[s.t];
+        s.restart_at = a.run->restart_at;
+      }
     } else {
       s.c1 = a.coeff1[s.t];
       s.c2 = a.coeff2[s.t];
@@ -1526,7 +1549,7 @@ struct TailMom {
 // expression, and adds the x0 the step used to the thread's moments mom (fp32, no contraction, the thread's items in
 // call order).
 template <int EPI>
-__device__ __forceinline__ bool tail_finish(const TailArgs& a, const TailStep& s, size_t o, float xv, float e,
+__device__ __forceinline__ bool tail_finish(const TailArgs& a, const TailStepOf<EPI>& s, size_t o, float xv, float e,
                                             TailMom& mom) {
 #pragma clang fp contract(off)
   if constexpr (kTailMode<EPI> == kTailX0) {
@@ -1536,14 +1559,25 @@ __device__ __forceinline__ bool tail_finish(const TailArgs& a, const TailStep& s
   if constexpr (tail_x0_form(kTailMode<EPI>)) {
     float x0 = s.a0 * xv - s.b0 * e;
     if (a.clip_x0) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-    if constexpr (kTailMode<EPI> == kTailX0StepMom) {
+    if constexpr (tail_traced(kTailMode<EPI>)) {
       const float sq = x0 * x0;
       mom.s = mom.s + x0;
       mom.q = mom.q + sq;
       mom.lo = fminf(mom.lo, x0);
       mom.hi = fmaxf(mom.hi, x0);
     }
-    float xn = (s.c1 * x0) + (s.c2 * xv);
+    float xn;
+    if constexpr (tail_2m(kTailMode<EPI>)) {
+      if (s.cp != 0.f) {  // (one row a launch: uniform, and so is the restart test)
+        const float x0p = s.t == s.restart_at ? x0 : a.hist[o];
+        xn = ((s.c1 * x0) + (s.cp * x0p)) + (s.c2 * xv);
+      } else {
+        xn = (s.c1 * x0) + (s.c2 * xv);
+      }
+      a.hist[o] = x0;
+    } else {
+      xn = (s.c1 * x0) + (s.c2 * xv);
+    }
     if (s.sv != 0.f) {  // (one row a launch: uniform)
       const float z = a.noise ? a.noise[(size_t)s.t * a.n * 3 * (a.H * a.W) + o]
                               : philox_normal(s.seed, (unsigned)s.t, (unsigned long long)(s.noise_offset + (long long)o));
@@ -1597,8 +1631,8 @@ __device__ __forceinline__ void tail_sse_item(const TailArgs& a, size_t o, int i
 // img, its x value xv and the step's scalars. The sse mode keeps the pair apart; every other mode guides it (no
 // contraction, this operand order) and ends in tail_finish. Returns whether the step's new x is NaN.
 template <int EPI, typename EU>
-__device__ __forceinline__ bool tail_item(const TailArgs& a, const TailStep& s, size_t o, int img, float xv, float ec,
-                                          EU&& eu, TailMom& mom) {
+__device__ __forceinline__ bool tail_item(const TailArgs& a, const TailStepOf<EPI>& s, size_t o, int img, float xv,
+                                          float ec, EU&& eu, TailMom& mom) {
   if constexpr (kTailMode<EPI> == kTailSse) {
     tail_sse_item(a, o, img, ec, a.cfg ? eu() : 0.f, mom.s, mom.q);
     return false;
@@ -1704,7 +1738,7 @@ __global__ __launch_bounds__(256) void tail_kernel(TailArgs a) {
   float eps[3], u[3] = {0.f, 0.f, 0.f};
   conv3(img, eps[0], eps[1], eps[2]);
   if (a.cfg) conv3(img + a.n, u[0], u[1], u[2]);
-  const TailStep st = tail_step_load<EPI>(a);
+  const TailStepOf<EPI> st = tail_step_load<EPI>(a);
   TailMom mom;
   bool bad = false;
 #pragma unroll
@@ -1837,7 +1871,7 @@ __global__ __launch_bounds__(NTH, 2) void tail_mfma_kernel(TailArgs a) {
   // latency hides behind the halo staging and the MFMAs
   constexpr int TIT = (TM_PX * 3 + NTH - 1) / NTH;
   float xpre[TIT] = {};
-  TailStep st;
+  TailStepOf<EPI> st;
   if (tail_reads_x(tail_mode<EPI>(a))) {
     st = tail_step_load<EPI>(a);
 #pragma unroll
@@ -1977,11 +2011,13 @@ __global__ __launch_bounds__(64) void tail_stats_finalize_kernel(const float* pa
 }
 
 // kTailX0 needs its operands (and nothing of the step's); the x0-form step its tables and the step's run state;
-// kTailSse its two outputs; kTailX0StepMom what the x0-form step needs and a trace that holds the batch
+// kTailSse its two outputs; the Mom modes what their step needs and a trace that holds the batch; the 2M modes the
+// x0-form step's operands, the cp table and the history
 static bool tail_x0_ok(const TailArgs& a) {
-  if (a.step_mode < kTailEps || a.step_mode > kTailX0StepMom) return false;
+  if (a.step_mode < kTailEps || a.step_mode > kTailX0Step2MMom) return false;
   if (a.step_mode == kTailSse) return a.vpart && a.vsse;
-  if (a.step_mode == kTailX0StepMom && !(a.tpart && a.trace && a.trace_rows >= 1 && a.trace_stride >= a.n))
+  if (tail_2m(a.step_mode) && !(a.xcp && a.hist)) return false;
+  if (tail_traced(a.step_mode) && !(a.tpart && a.trace && a.trace_rows >= 1 && a.trace_stride >= a.n))
     return false;
   if (tail_x0_form(a.step_mode)) {
     for (const float* p : a.xrow)
@@ -1997,7 +2033,7 @@ template <int E> using TailEpi = std::integral_constant<int, E>;
 // The body of a tail launcher from its launch geometry on: launches the instantiation a.step_mode selects of one kernel
 // family and returns the launch's status. FAMILY names the family, an expression in E, the instantiation's EPI; PLAIN
 // is its E = 0 member once more, spelled as the census has always recorded it (ITSD_LAUNCH records the expression's
-// text, and the census and the profiles key on that of the forward and the ancestral step). BIG: the five may use up
+// text, and the census and the profiles key on that of the forward and the ancestral step). BIG: all of them may use up
 // to kTailSmemMax of dynamic shared memory; the attribute is set once. PXB: the pixels of a block. The modes that end
 // in statistics are followed by their finalize launch, and are refused where a block would straddle two images (an
 // image is not a whole number of blocks).
@@ -2008,7 +2044,8 @@ template <int E> using TailEpi = std::integral_constant<int, E>;
       return FAMILY;                                                                                                 \
     };                                                                                                               \
     const TailKernel kern[] = {member(TailEpi<0>{}), member(TailEpi<1>{}), member(TailEpi<2>{}),                     \
-                               member(TailEpi<3>{}), member(TailEpi<4>{})};                                          \
+                               member(TailEpi<3>{}), member(TailEpi<4>{}), member(TailEpi<5>{}),                     \
+                               member(TailEpi<6>{})};                                                                \
     static bool attr = !(BIG);                                                                                       \
     if (!attr) {                                                                                                     \
       for (const TailKernel f : kern) {                                                                              \
@@ -2023,7 +2060,7 @@ template <int E> using TailEpi = std::integral_constant<int, E>;
     if (epi == 0) ITSD_LAUNCH(PLAIN, grid, block, sm, s, a);                                                         \
     else ITSD_LAUNCH(kern[epi], grid, block, sm, s, a);                                                              \
     if (nst) {                                                                                                       \
-      const bool traced = (a).step_mode == kTailX0StepMom;                                                           \
+      const bool traced = tail_traced((a).step_mode);                                                                \
       ITSD_LAUNCH(tail_stats_finalize_kernel, dim3((nst * (a).n + 63) / 64), dim3(64), 0, s,                         \
                   traced ? (a).tpart : (a).vpart, (a).H * (a).W / (PXB), (a).n, nst, traced ? (a).tsel : nullptr,    \
                   traced ? (a).trace : (a).vsse, traced ? (a).trace_rows : 1, traced ? (a).trace_stride : (a).n);    \
@@ -2053,7 +2090,7 @@ hipError_t launch_tail(const TailArgs& a, hipStream_t s) {
   ITSD_RETURN_TAIL_LAUNCH(tail_kernel<T>, (tail_kernel<T, E>), false, 256, grid, dim3(256), 27 * a.C * sizeof(float), s,
                           a);
 }
-// Whether the per-block statistics of kTailSse / kTailX0StepMom are refused at this geometry: launch_tail (not the MFMA tail, whose
+// Whether the per-block statistics of kTailSse / the Mom modes are refused at this geometry: launch_tail (not the MFMA tail, whose
 // blocks are whole rows of one image) falls to tail_kernel and its 256-pixel blocks would straddle two images.
 bool tail_block_straddles(int H, int W, int C) {
   const bool tiled = W <= 64 && 64 % W == 0 && H % (64 / W) == 0 && C % 32 == 0;

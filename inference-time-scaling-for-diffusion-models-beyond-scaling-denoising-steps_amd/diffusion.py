@@ -19,6 +19,11 @@ is available by passing ``noise=`` (see ``reference_noise_plan``).
 (``schedule.strided_timesteps`` or an explicit list) and steps by DDIM(eta) written through the x_0 estimate, clipped to
 [-1, 1] under ``clip_x0`` (``schedule.x0_form_rows``, ``itsd_set_schedule_x0``). Every step argument of ``run`` and
 ``predict_x0``, the injected-noise index and the Philox stream id are then rows; ``n_steps`` is K.
+
+``sampler="dpmpp2m"`` walks the same rows second order: DPM-Solver++(2M) in data prediction, deterministic (eta = 0),
+with the previous row's x_0 estimate kept inside the library (``schedule.x0_2m_rows``, ``itsd_set_schedule_x0_2m``).
+A ``run`` starts first order at its top row unless ``cont=True`` continues the run before it. Everything else is as
+under ddim: ``X0_FORM`` names the two.
 """
 from __future__ import annotations
 
@@ -27,7 +32,10 @@ from typing import Optional, Sequence, Tuple
 
 import torch
 
-from .schedule import check_timesteps, make_schedule, strided_timesteps, x0_coeffs, x0_form_rows
+from .schedule import check_timesteps, make_schedule, strided_timesteps, x0_2m_rows, x0_coeffs, x0_form_rows
+
+X0_FORM = ("ddim", "dpmpp2m")  # the samplers that step rows through the x_0 estimate
+
 
 
 def _extract(v: torch.Tensor, t: torch.Tensor, ndim: int) -> torch.Tensor:
@@ -47,8 +55,8 @@ class GaussianDiffusionSampler:
         self.T = int(T)
         self.w = float(w)
         self.sched = make_schedule(beta_1, beta_T, T)
-        if sampler not in ("ddpm", "ddim"):
-            raise ValueError(f"sampler must be 'ddpm' or 'ddim', not {sampler!r}")
+        if sampler not in ("ddpm",) + X0_FORM:
+            raise ValueError(f"sampler must be 'ddpm', 'ddim' or 'dpmpp2m', not {sampler!r}")
         self.sampler = sampler
         # the reference's registered buffers (Diffusion.py:57-65)
         self.betas = self.sched.betas
@@ -57,7 +65,9 @@ class GaussianDiffusionSampler:
         self.posterior_var = self.sched.posterior_var
         self._sched_args = (self.sched.coeff1_f32, self.sched.coeff2_f32, self.sched.sqrt_var_f32, self.w)
         self.tau = list(range(self.T))  # row -> timestep (the identity for ddpm)
-        if sampler == "ddim":
+        if sampler in X0_FORM:
+            if sampler == "dpmpp2m" and float(eta) != 0.0:
+                raise ValueError(f"eta = {eta}: sampler='dpmpp2m' is deterministic (eta = 0)")
             if not 0.0 <= float(eta) <= 1.0:
                 raise ValueError(f"eta = {eta} outside [0, 1]")
             if steps is None or isinstance(steps, numbers.Integral):
@@ -65,21 +75,27 @@ class GaussianDiffusionSampler:
             else:
                 self.tau = check_timesteps(steps, self.T)
             self.eta, self.clip_x0 = float(eta), bool(clip_x0)
-            self.rows = x0_form_rows(self.sched.alphas_bar, self.tau, self.eta)
+            self.rows = (x0_2m_rows(self.sched.alphas_bar, self.tau) if sampler == "dpmpp2m" else
+                         x0_form_rows(self.sched.alphas_bar, self.tau, self.eta))
             self._sched_args = (self.tau, self.rows, self.clip_x0, self.w)
         elif steps is not None or eta != 0.0 or clip_x0:
-            raise ValueError("steps, eta and clip_x0 belong to sampler='ddim'")
+            raise ValueError("steps, eta and clip_x0 belong to sampler='ddim' / 'dpmpp2m'")
         self.last_seed = None  # Philox key of the last run (set by run)
 
     @property
+    def x0_form(self) -> bool:
+        """Whether the sampler steps rows through the x_0 estimate (ddim, dpmpp2m)."""
+        return self.sampler in X0_FORM
+
+    @property
     def n_steps(self) -> int:
-        """Rows a full run walks: T for ddpm, K for ddim."""
+        """Rows a full run walks: T for ddpm, K for ddim / dpmpp2m."""
         return len(self.tau)
 
     @property
     def abar_rows(self) -> torch.Tensor:
-        """alphas_bar by row (fp64): abar[tau] for ddim, ``sched.alphas_bar`` itself for ddpm."""
-        if self.sampler == "ddpm":
+        """alphas_bar by row (fp64): abar[tau] for ddim / dpmpp2m, ``sched.alphas_bar`` itself for ddpm."""
+        if not self.x0_form:
             return self.sched.alphas_bar
         return self.sched.alphas_bar[torch.tensor(self.tau, dtype=torch.long)]
 
@@ -94,7 +110,8 @@ class GaussianDiffusionSampler:
     def _native(self, n: int):
         nat = self.model.native(n)
         if getattr(nat, "_sched_args", None) is not self._sched_args:
-            (nat.set_schedule_x0 if self.sampler == "ddim" else nat.set_schedule)(*self._sched_args)
+            install = {"ddpm": nat.set_schedule, "ddim": nat.set_schedule_x0, "dpmpp2m": nat.set_schedule_x0_2m}
+            install[self.sampler](*self._sched_args)
             nat._sched_args = self._sched_args
         return nat
 
@@ -118,10 +135,10 @@ class GaussianDiffusionSampler:
         """A score trace for runs of up to n images: a NaN-filled fp64 device tensor [n_steps, n, 4]. Passed to
         ``run(.., trace=)``, row k receives (sum, sum of squares, min, max) of the x_0 estimate step k used for each
         image (``itsd_sampler_set_trace``); rows not run keep their NaN. It carries ``per_image`` = 3 H W, the D of
-        ``verifier.moment_scores``. ddim only: the ancestral step never forms x_0."""
-        if self.sampler != "ddim":
-            raise ValueError("a score trace needs sampler='ddim': the ancestral step has no x_0 rows (ddim with "
-                             "steps=T, eta=1 is its x0-form equivalent)")
+        ``verifier.moment_scores``. ddim / dpmpp2m only: the ancestral step never forms x_0."""
+        if not self.x0_form:
+            raise ValueError("a score trace needs sampler='ddim' or 'dpmpp2m': the ancestral step has no x_0 rows "
+                             "(ddim with steps=T, eta=1 is its x0-form equivalent)")
         if int(n) < 1:
             raise ValueError(f"a trace holds n >= 1 images, not {n}")
         t = torch.full((self.n_steps, int(n), 4), float("nan"), dtype=torch.float64, device=self.model.device)
@@ -131,12 +148,14 @@ class GaussianDiffusionSampler:
 
     def run(self, x: torch.Tensor, t_begin: Optional[int] = None, t_end: int = 0, labels=None, seed=None,
             noise: Optional[torch.Tensor] = None, noise_offset: int = 0, graph: bool = True, clip=None,
-            sync: bool = True, trace: Optional[torch.Tensor] = None) -> torch.Tensor:
+            sync: bool = True, trace: Optional[torch.Tensor] = None, cont: bool = False) -> torch.Tensor:
         """In-place steps t_begin..t_end on a contiguous fp32 device tensor x (rows of the schedule: timesteps for
-        ddpm). ``trace`` (``new_trace``; ddim only) is attached for this call and detached after it: x is the untraced
-        run's bit for bit, and trace[k, :len(x)] holds the x_0 moments of every row k run."""
-        if trace is not None and self.sampler != "ddim":
-            raise ValueError("run(trace=) needs sampler='ddim': the ancestral step has no x_0 rows")
+        ddpm). ``trace`` (``new_trace``; ddim / dpmpp2m only) is attached for this call and detached after it: x is the
+        untraced run's bit for bit, and trace[k, :len(x)] holds the x_0 moments of every row k run. ``cont`` (dpmpp2m
+        only; ``ITSD_RUN_CONTINUE``): the step at t_begin is second order on the x_0 the previous run left at row
+        t_begin + 1 for the same batch; without it a run's first step is first order."""
+        if trace is not None and not self.x0_form:
+            raise ValueError("run(trace=) needs sampler='ddim' or 'dpmpp2m': the ancestral step has no x_0 rows")
         t_begin = self.n_steps - 1 if t_begin is None else int(t_begin)
         if clip is None:
             clip = t_end == 0
@@ -152,12 +171,12 @@ class GaussianDiffusionSampler:
         nat = self._native(x.shape[0])
         if trace is None:
             nat.run(x, t_begin, t_end, seed or 0, noise=noise, labels=labels, noise_offset=noise_offset, graph=graph,
-                    clip=clip, sync=sync)
+                    clip=clip, sync=sync, cont=cont)
             return x
         nat.set_trace(trace)
         try:
             nat.run(x, t_begin, t_end, seed or 0, noise=noise, labels=labels, noise_offset=noise_offset, graph=graph,
-                    clip=clip, sync=sync)
+                    clip=clip, sync=sync, cont=cont)
         finally:  # (host state: steps already queued keep the pointer their launches were given)
             nat.set_trace(None)
         return x
@@ -190,7 +209,8 @@ class GaussianDiffusionSampler:
         """The T-1 draws one reference sampler call takes from the global CPU generator
         (``Diffusion.py:94-96``: ``randn_like`` at t = T-1 .. 1), as [T, *shape] by step t."""
         if self.sampler != "ddpm":
-            raise ValueError("the reference has no few-step sampler: there is no reference draw order under ddim")
+            raise ValueError("the reference has no few-step sampler: there is no reference draw order under "
+                             f"{self.sampler}")
         z = [torch.randn(tuple(shape)) for _ in range(self.T - 1)]
         return torch.stack(z + [torch.zeros(tuple(shape))]).flip(0)
 
@@ -201,7 +221,8 @@ class GaussianDiffusionSampler:
         loop under ``torch.manual_seed``); otherwise Philox seeded from that generator."""
 
         if reference_rng and self.sampler != "ddpm":
-            raise ValueError("reference_rng=True needs sampler='ddpm': the reference has no draw order for ddim")
+            raise ValueError("reference_rng=True needs sampler='ddpm': the reference has no draw order for "
+                             f"{self.sampler}")
 
         def fn(noise: torch.Tensor, show_progress: bool = False, **kw) -> torch.Tensor:
             z = self.reference_noise(noise.shape) if reference_rng else None

@@ -64,12 +64,14 @@ Keys beyond the reference (all optional):
   counterpart: the reference has the ancestral sampler only). Absent, or ``kind: ddpm``: the ancestral sampler::
 
       sampler:
-        kind: ddim               # ddpm | ddim
+        kind: ddim               # ddpm | ddim | dpmpp2m
         steps: 50                # rows K in [1, inference T] (default: T); strided over the T timesteps
-        eta: 0.0                 # in [0, 1]: 0 deterministic, 1 the ancestral variance
+        eta: 0.0                 # ddim: in [0, 1], 0 deterministic, 1 the ancestral variance; dpmpp2m: 0 or absent
         clip_x0: true            # clip the x_0 estimate inside every step (bounded trajectories)
 
-  Under ddim the search block's ``injection_step`` / ``renoise_steps`` count rows. ``sampler.steps=20`` overrides work
+  ``kind: dpmpp2m`` walks the same rows with the second-order multistep step (DPM-Solver++(2M)):
+  ``sampler: {kind: dpmpp2m, steps: 20, clip_x0: true}``. Under ddim and dpmpp2m the search block's
+  ``injection_step`` / ``renoise_steps`` count rows. ``sampler.steps=20`` overrides work
   as for ``search.*``.
 
 There is no training entry: ``state: train`` raises (training is out of scope).
@@ -437,8 +439,8 @@ def sampler_kwargs(cfg: Dict[str, Any], T: int) -> Dict[str, Any]:
         raise ValueError(f"unknown sampler keys {sorted(unknown)} (kind | steps | eta | clip_x0)")
     kind = s.get("kind", "ddpm")
     kind = kind.lower() if isinstance(kind, str) else kind
-    if kind not in ("ddpm", "ddim"):
-        raise ValueError(f"unknown sampler.kind '{kind}' (ddpm | ddim)")
+    if kind not in ("ddpm", "ddim", "dpmpp2m"):
+        raise ValueError(f"unknown sampler.kind '{kind}' (ddpm | ddim | dpmpp2m)")
     steps, eta, clip = s.get("steps"), s.get("eta", 0.0), s.get("clip_x0", False)
     if steps is not None and (isinstance(steps, bool) or not isinstance(steps, int) or not 1 <= steps <= int(T)):
         raise ValueError(f"sampler.steps = {steps!r} must be an integer in [1, inference T = {int(T)}]")
@@ -448,9 +450,11 @@ def sampler_kwargs(cfg: Dict[str, Any], T: int) -> Dict[str, Any]:
         raise ValueError(f"sampler.clip_x0 = {clip!r} must be true or false")
     if kind == "ddpm":
         if steps not in (None, int(T)) or eta != 0.0 or clip:
-            raise ValueError("sampler.steps / eta / clip_x0 need sampler.kind: ddim")
+            raise ValueError("sampler.steps / eta / clip_x0 need sampler.kind: ddim | dpmpp2m")
         return {}
-    return {"sampler": "ddim", "steps": steps, "eta": float(eta), "clip_x0": clip}
+    if kind == "dpmpp2m" and eta != 0.0:
+        raise ValueError(f"sampler.eta = {eta!r}: sampler.kind dpmpp2m is deterministic (eta must be 0 or absent)")
+    return {"sampler": kind, "steps": steps, "eta": float(eta), "clip_x0": clip}
 
 
 def search_verifier(s: Dict[str, Any], sampler, has_labels: bool):
@@ -493,7 +497,7 @@ def particle_args(cfg: Dict[str, Any], T: int) -> Dict[str, Any]:
     s = cfg.get("search") or {}
     kw = sampler_kwargs(cfg, T)
     if kw.get("sampler") != "ddim" or not kw["eta"] > 0:
-        raise ValueError("sampler.kind / sampler.eta: search.algorithm particle needs kind: ddim and eta > 0 (the score trace is the "
+        raise ValueError("sampler.kind / sampler.eta: search.algorithm particle needs kind: ddim and eta > 0, not ddpm or dpmpp2m (the score trace is the "
                          "x0-form step's, and copies of a parent diverge only through the step noise)")
     rows = int(T if kw["steps"] is None else kw["steps"])
 

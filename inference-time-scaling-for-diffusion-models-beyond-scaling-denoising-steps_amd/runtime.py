@@ -24,7 +24,7 @@ ITSD_OK, ITSD_ERR_INVALID, ITSD_ERR_HIP, ITSD_ERR_WEIGHTS, ITSD_ERR_NAN, ITSD_ER
 PREC_FP32, PREC_BF16 = 0, 1
 VERIFY_ORACLE, VERIFY_SELFSUP, VERIFY_AESTHETIC, VERIFY_MEAN = 0, 1, 2, 3
 VERIFY_DENOISE = 16  # DenoisingVerifier: scored by itsd_verify_denoise on a UNet handle, not an itsd_verify kind
-RUN_GRAPH, RUN_CLIP, RUN_SYNC = 1, 2, 4
+RUN_GRAPH, RUN_CLIP, RUN_SYNC, RUN_CONTINUE = 1, 2, 4, 8
 
 
 class ItsdError(RuntimeError):
@@ -94,6 +94,7 @@ _SIGS = {
     "itsd_set_schedule": [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                           ctypes.c_float],
     "itsd_set_schedule_x0": [ctypes.c_void_p, ctypes.POINTER(X0Schedule)],
+    "itsd_set_schedule_x0_2m": [ctypes.c_void_p, ctypes.POINTER(X0Schedule), ctypes.c_void_p],
     "itsd_sampler_run": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                          ctypes.c_uint64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p],
     "itsd_sampler_set_trace": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int],
@@ -250,10 +251,12 @@ class NativeUNet:
         check(lib().itsd_set_schedule(self.h, c1.numel(), c1.data_ptr(), c2.data_ptr(), sv.data_ptr(), float(w)))
         self.T_sched = c1.numel()
 
-    def set_schedule_x0(self, tau: Sequence[int], rows: Dict[str, torch.Tensor], clip_x0: bool, w: float = 0.0):
+    def set_schedule_x0(self, tau: Sequence[int], rows: Dict[str, torch.Tensor], clip_x0: bool, w: float = 0.0,
+                        two_m: bool = False):
         """Install an x0-form schedule (``itsd_set_schedule_x0``): ``tau`` the timestep of each row, ``rows`` the five
         per-row tables a0, b0, c0, cx, sg (``schedule.x0_form_rows``; cast to fp32 here). ``run`` and ``predict_x0``
-        then count rows; ``set_schedule`` puts the ancestral form back."""
+        then count rows; ``set_schedule`` puts the ancestral form back. ``two_m``: the second-order form
+        (``itsd_set_schedule_x0_2m``), whose ``rows`` (``schedule.x0_2m_rows``) hold a sixth table cp."""
         K = len(tau)
         sc = X0Schedule()
         sc.K = K
@@ -267,13 +270,23 @@ class NativeUNet:
             setattr(sc, k, ctypes.cast(v.data_ptr(), ctypes.POINTER(ctypes.c_float)))
         sc.clip_x0 = int(bool(clip_x0))
         sc.w = float(w)
-        check(lib().itsd_set_schedule_x0(self.h, ctypes.byref(sc)))
+        if two_m:
+            cp = rows["cp"].detach().cpu().float().contiguous()
+            if cp.numel() != K:
+                raise ValueError(f"x0-form table cp has {cp.numel()} rows, tau has {K}")
+            check(lib().itsd_set_schedule_x0_2m(self.h, ctypes.byref(sc), cp.data_ptr()))
+        else:
+            check(lib().itsd_set_schedule_x0(self.h, ctypes.byref(sc)))
         self.T_sched = K
+
+    def set_schedule_x0_2m(self, tau: Sequence[int], rows: Dict[str, torch.Tensor], clip_x0: bool, w: float = 0.0):
+        self.set_schedule_x0(tau, rows, clip_x0, w, two_m=True)
 
     def run(self, x: torch.Tensor, t_begin: int, t_end: int, seed: int, noise: Optional[torch.Tensor] = None,
             labels: Optional[torch.Tensor] = None, noise_offset: int = 0, graph: bool = True, clip: bool = True,
-            sync: bool = True) -> None:
-        flags = (RUN_GRAPH if graph else 0) | (RUN_CLIP if clip else 0) | (RUN_SYNC if sync else 0)
+            sync: bool = True, cont: bool = False) -> None:
+        flags = (RUN_GRAPH if graph else 0) | (RUN_CLIP if clip else 0) | (RUN_SYNC if sync else 0) | \
+                (RUN_CONTINUE if cont else 0)
         check(lib().itsd_sampler_run(self.h, x.data_ptr(), _ptr(labels), x.shape[0], int(t_begin), int(t_end),
                                      int(seed) & ((1 << 64) - 1), int(noise_offset), _ptr(noise), flags,
                                      stream_ptr(x.device)))

@@ -127,3 +127,32 @@ def x0_form_rows(alphas_bar: torch.Tensor, tau: Sequence[int], eta: float) -> Di
                         ("cx", d / math.sqrt(1.0 - a)), ("sg", sg)):
             rows[name].append(v)
     return {k: torch.tensor(v, dtype=torch.float64) for k, v in rows.items()}
+
+
+def x0_2m_rows(alphas_bar: torch.Tensor, tau: Sequence[int]) -> Dict[str, torch.Tensor]:
+    """The per-row scalars of the second-order multistep x0-form step, DPM-Solver++(2M) in data prediction, fp64 [K]
+    each: ``x0_form_rows(alphas_bar, tau, eta=0.0)``'s five tables with c0 replaced, and a sixth, cp:
+
+        x0 = a0 x - b0 eps  (clipped by a clip_x0 sampler);   x' = c0 x0 + cp x0_prev + cx x
+
+    x0_prev the estimate of row k + 1, the row before this one. With lambda_k = ln(abar[tau[k]] / (1 - abar[tau[k]])) / 2,
+    h = lambda_{k-1} - lambda_k, r = (lambda_k - lambda_{k+1}) / h and c0d the first-order c0:
+    c0[k] = c0d[k] (1 + 1/(2r)), cp[k] = -c0d[k] / (2r) for 1 <= k <= K - 2. Row K - 1 has no predecessor and row 0
+    an infinite last lambda gap: both keep c0d with cp = 0 (first order), and row 0 stays (1, 0, 0). sg is all zeros."""
+    tau = [int(t) for t in tau]
+    rows = x0_form_rows(alphas_bar, tau, 0.0)
+    K = len(tau)
+    lam = []
+    for t in tau:
+        a = float(alphas_bar[t].double())
+        lam.append(0.5 * math.log(a / (1.0 - a)))
+    c0, cp = rows["c0"].clone(), torch.zeros(K, dtype=torch.float64)
+    for k in range(1, K - 1):
+        h = lam[k - 1] - lam[k]
+        r = (lam[k] - lam[k + 1]) / h
+        c0d = float(rows["c0"][k])
+        c0[k] = c0d * (1.0 + 1.0 / (2.0 * r))
+        cp[k] = -c0d / (2.0 * r)
+    rows["c0"] = c0
+    rows["cp"] = cp
+    return rows

@@ -541,7 +541,8 @@ class SearchEngine:
         x_s, its x_0 estimate is scored, the ``keep`` best survive with N // keep children each, and the children are
         the survivor re-noised ``renoise_steps`` steps up (0: a copy; they then diverge through the sampler's own
         per-step noise, which is keyed by position). After the last stage the paths are denoised to the end and scored
-        as in ``path_search``.
+        as in ``path_search``. Under the second-order sampler (dpmpp2m) every window is a restarted run -- its first
+        step is first order -- because re-noised children have no valid x_0 history.
 
         Returns (best_noise, best_score, hist). best_noise is the initial noise of the winner's ROOT ancestor;
         re-denoising it does NOT reproduce the winner, because the branch draws and the per-window sampler keys are
@@ -643,7 +644,8 @@ class SearchEngine:
             raise ValueError("fk_search scores particles from the sampler's x_0 moments: the verifier needs a "
                              "trace_kind (OracleVerifier, AestheticPredictor)")
         if getattr(self.sampler, "sampler", "ddpm") != "ddim":
-            raise ValueError("fk_search needs sampler='ddim': the ancestral step leaves no score trace")
+            raise ValueError("fk_search needs sampler='ddim' with eta > 0: the ancestral step (ddpm) leaves no score "
+                             "trace, and dpmpp2m is deterministic (copies of a parent would never diverge)")
         sg = self.sampler.rows["sg"]
         if float(getattr(self.sampler, "eta", 0.0)) == 0.0 or not bool((torch.as_tensor(sg) != 0).any()):
             raise ValueError("fk_search needs eta > 0 and a non-zero sg row: copies of a parent diverge only through "

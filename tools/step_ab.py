@@ -9,6 +9,9 @@ evaluations; --eta, --clip-x0) side by side, interleaved like the variants.
 --trace times the x0-form step with a score trace attached (the "x0 step + moments" tail and its finalize launch)
 against the same build's untraced x0-form step, alternating in one process: arms untraced, traced, untraced again --
 the second untraced arm is the A/A spread the difference is read against.
+
+--samplers ddim,dpmpp2m times the second-order step against the x0-form step (--eta is ddim's; dpmpp2m is eta = 0); a
+kind may be listed twice (ddim,ddim) for the A/A spread of one step against itself.
 """
 import argparse
 import os
@@ -69,7 +72,8 @@ def main():
     ap.add_argument("--create-set", default="", help="options set before the UNet is created, e.g. attn_fuse=0")
     ap.add_argument("--lib", default="", help="another build of libitsd_hip.so (A/B of two builds in two processes)")
     ap.add_argument("--arch", default="a", help="a: Arch A; c: the C3 leg (Arch C CondUNet, CFG w=1.8: --n is N, 2N guided)")
-    ap.add_argument("--samplers", default="ddpm", help="ddpm (the ancestral step), ddim (the x0-form step), or both: ddpm,ddim")
+    ap.add_argument("--samplers", default="ddpm", help="a comma list of ddpm (the ancestral step), ddim (the x0-form step), dpmpp2m (the 2M step); a kind "
+                         "listed twice is timed as two arms (A/A)")
     ap.add_argument("--eta", type=float, default=1.0, help="ddim: eta (0: no draw at all)")
     ap.add_argument("--clip-x0", type=int, default=1, help="ddim: clip the x_0 estimate (0 | 1)")
     ap.add_argument("--trace", action="store_true", help="the traced against the untraced ddim step (and an A/A arm)")
@@ -97,8 +101,19 @@ def main():
                    weights="gauss").to("cuda:0")
         make = lambda **kw: GaussianDiffusionSampler(net, 1e-4, 0.02, 1000, **kw)
     kinds = args.samplers.split(",")
-    smps = {k: make() if k == "ddpm" else make(sampler="ddim", steps=1000, eta=args.eta, clip_x0=bool(args.clip_x0))
-            for k in kinds}
+    kinds = [k if kinds.count(k) == 1 else f"{k}#{kinds[:i].count(k)}" for i, k in enumerate(kinds)]  # ddim#0, ddim#1
+
+    def sampler_of(kind):
+        kind = kind.split("#")[0]
+        if kind == "ddpm":
+            return make()
+        if kind == "dpmpp2m":
+            return make(sampler="dpmpp2m", steps=1000, clip_x0=bool(args.clip_x0))
+        if kind != "ddim":
+            raise SystemExit(f"--samplers: unknown kind {kind!r} (ddpm | ddim | dpmpp2m)")
+        return make(sampler="ddim", steps=1000, eta=args.eta, clip_x0=bool(args.clip_x0))
+
+    smps = {k: sampler_of(k) for k in kinds}
     x = torch.randn(args.n, 3, args.img, args.img, device="cuda")
     variants = [v if len(kinds) == 1 else f"{v}/{k}" for v in args.variants.split(",") for k in kinds]
     if args.trace:
