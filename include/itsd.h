@@ -22,6 +22,9 @@
  *                                   ancestral form stays the default and the parity contract
  *   itsd_set_schedule_x0_2m      <- (no reference counterpart) the same K rows stepped second order: DPM-Solver++(2M)
  *                                   in data prediction, with the previous row's x_0 estimate kept by the library
+ *   itsd_set_guidance            <- the guided eps of DiffusionCondition.py:79-87 with w a function of (row, candidate
+ *                                   image): guidance schedules (intervals, ramps) and a per-candidate scale a search
+ *                                   can sweep, under one captured step graph; rows with w = 0 skip the uncond half
  *   itsd_sampler_predict_x0      <- (no reference counterpart) the x_0 estimate of a half-denoised state, what a
  *                                   verifier can score mid-trajectory: the branching PathSearch its docstring
  *                                   describes (search/search_algorithm.py:238-250; its code, :307-312, is a placeholder)
@@ -187,6 +190,34 @@ int itsd_set_schedule_x0(itsd_unet* u, const itsd_x0_schedule* schedule);
  * ITSD_ERR_INVALID with a message naming this function, before any HIP call: everything itsd_set_schedule_x0 refuses,
  * a null cp, a cp[k] that is not finite, cp[K-1] != 0. */
 int itsd_set_schedule_x0_2m(itsd_unet* u, const itsd_x0_schedule* schedule, const float* cp);
+
+/* DiffusionCondition.py:79-87 with w a function of (row, image). Host pointers; the library copies them.
+ * w_rows [rows] fp32, or NULL = every row the schedule's scalar w; w_img [n_img] fp32 multipliers, or NULL = 1.
+ * Both NULL detaches.
+ * While attached, the x0-form step of itsd_sampler_run at row k guides candidate image i (never i + n) with
+ *   w = w_rows[k] ; if (w_img) w = w * w_img[i] ; w1 = 1.0f + w ; eps = w1 * eps_c - w * eps_u
+ * in fp32 without contraction, read on the device from library-owned buffers whose addresses never change: installing
+ * new values needs no new graph capture. With w_img NULL and w_rows[k] the schedule's scalar these are the scalar
+ * path's bits. The upload is ordered on the handle's stream behind every run already queued (which keeps the values it
+ * was queued under) and the call returns when it is done.
+ * Cond-only rows: a row with w_rows[k] == 0.0f (the host's copy decides; w_img cannot turn a guided row into one) has
+ * eps = eps_c, and its step runs a second program on the n conditional images alone -- half the UNet batch -- through
+ * the same step mode's unguided form. Graph mode keeps one graph for each program (the cache key holds "table
+ * attached" and "cond-only"). The score trace and the 2M history work on both kinds of row; on a cond-only row the
+ * history receives the unguided x0. itsd_set_option("cfg_skip", 0) runs such rows on the doubled batch through the
+ * table instead. The two programs pick kernels by batch, so a cond-only row equals its doubled-batch form to rounding,
+ * not to the bit.
+ * itsd_unet_query: "guidance" = 0 none, 1 rows, 2 rows and per-image multipliers; "cond_only_steps" = steps of the
+ * last itsd_sampler_run that ran the cond-only program.
+ * itsd_sampler_predict_x0 at row t guides with w_rows[t] as its scalar, and answers ITSD_ERR_INVALID while per-image
+ * multipliers are installed; itsd_verify_denoise ignores the table (the probe is unguided). Installing a schedule
+ * (any of the three calls) detaches.
+ * ITSD_ERR_INVALID with a message naming this function, before any HIP call: a null handle; a non-CFG handle; no
+ * x0-form schedule installed (the ancestral form keeps its scalar; ddim with steps = T, eta = 1 is its x0-form
+ * equivalent); rows != T_sched; n_img outside [1, max_batch]; a non-finite entry; a tail geometry whose blocks would
+ * straddle two images. At run time itsd_sampler_run answers ITSD_ERR_INVALID for n > n_img while multipliers are
+ * installed, before any launch. */
+int itsd_set_guidance(itsd_unet* u, const float* w_rows, int rows, const float* w_img, int n_img);
 
 /* Run steps t_begin..t_end (inclusive, descending) of the ancestral sampler in
  * place on x[n,3,H,W]. With ITSD_RUN_GRAPH one denoising step is captured per
@@ -364,7 +395,8 @@ int itsd_profile_op(itsd_unet* u, const float* x, const int32_t* t, int n, int o
  * and meaning): kernel and tile choices ("conv_variant", "splitk" 0/1, "splitk_inl", "subpix_split", "conv1x1" 0/1,
  * "small_conv", "small_8x8", "small_wide", "small_gn", "gn_wide", "gn_fold", "p4_w", "p4_c96", "p4_sub", "p4_plain",
  * "p5", "p5_split", "p5_sc", "p5_pub", "p5_xl", "p5_dist", "convt_prune", "attn_split", "attn_wide",
- * "attn_wide_nq"), the in-kernel hand-off poll bound ("spin_bound"), and build-time choices read at create
+ * "attn_wide_nq"), the in-kernel hand-off poll bound ("spin_bound"), the cond-only step of w = 0 guidance rows
+ * ("cfg_skip" 0/1, itsd_set_guidance), and build-time choices read at create
  * ("fuse_gn", "io_mfma", "attn_fuse", "attn_s1", "tap_prune", "down_merge"). Defaults are the shipped choices; every
  * alternative is covered by a parity test. Measurement switches of measured-and-dropped variants ("conv_dbg",
  * "attn_cs", "attn_aq", "p4_xcd", "small_minks", "p5_c64", forced "splitk" slice counts, "conv1x1" 2) exist in
@@ -374,7 +406,7 @@ int itsd_set_option(const char* key, int value);
 
 /* Introspection of a handle (no device work): "graph_captures" (step graphs captured and
  * instantiated so far; a search replays one graph across all its rounds), "max_batch",
- * "T_sched" (timesteps, or the rows K of an x0-form schedule), "sched_form" (0 ancestral, 1 x0-form, 2 the 2M x0-form), "trace" (1 while a score trace is attached), "ws_bytes"
+ * "T_sched" (timesteps, or the rows K of an x0-form schedule), "sched_form" (0 ancestral, 1 x0-form, 2 the 2M x0-form), "trace" (1 while a score trace is attached), "guidance" and "cond_only_steps" (itsd_set_guidance), "ws_bytes"
  * (activation arena), "ops" (program length); and, synchronising the
  * handle's stream, "status" = the in-kernel hand-off status word of the last forward / sampler run
  * (0 ok; bit 0: attn_block_split_kernel's wait exhausted its bound, bit 1: conv3x3_gn_p5_kernel's shared split-K

@@ -55,6 +55,7 @@ bool tail_mfma_ok(int H, int W, int C);
 bool tail_block_straddles(int H, int W, int C);
 int g_io_mfma = 1;  // bf16 head / tail on MFMA (itsd_set_option "io_mfma", read at create)
 int g_small_gn = 1;  // conv_small writes its consumer GroupNorm's output (itsd_set_option "small_gn"): 0 off, 1 on
+int g_cfg_skip = 1;  // w == 0 rows of a guidance table run the cond-only step program (itsd_set_option "cfg_skip")
 hipError_t launch_noise(float*, const float*, int, long long, float, unsigned long long, unsigned, long long,
                         hipStream_t);
 hipError_t launch_branch(float*, const float*, const int*, int, long long, float, float, unsigned long long, unsigned,
@@ -172,8 +173,8 @@ struct Arena {
 // staged through handle-owned buffers and the seed, noise offset and clip step live in device
 // memory (RunParams), so every round of a search replays one graph.
 struct GraphEntry {
-  // (n, labels, noise, option generation, schedule form, trace, trace stride)
-  std::tuple<int, bool, const float*, int, int, const double*, int> key;
+  // (n, labels, noise, option generation, schedule form, trace, trace stride, guidance table 0 | 1 | 2, cond-only)
+  std::tuple<int, bool, const float*, int, int, const double*, int, int, bool> key;
   hipGraphExec_t exec = nullptr;
 };
 
@@ -227,6 +228,16 @@ struct itsd_unet {
   float* x0_hist = nullptr;
   int hist_row = -1, hist_n = 0;
   float guide_w = 0.f, guide_w1 = 1.f;
+  // the guidance table (itsd_set_guidance): guidance 0 none, 1 rows, 2 rows and per-image multipliers. gw_rows_h /
+  // gw_img_h are the host's copies (the cond-only decision and itsd_sampler_predict_x0's scalar read them); gw_rows_d
+  // [gw_rows_cap >= T_sched] and gw_img_d [max_batch] are the device's, allocated at the first attach and kept, so a
+  // re-install changes values under the captured graphs, never an address
+  int guidance = 0;
+  std::vector<float> gw_rows_h, gw_img_h;
+  float* gw_rows_d = nullptr;
+  int gw_rows_cap = 0;
+  float* gw_img_d = nullptr;
+  int cond_only_steps = 0;  // of the last itsd_sampler_run (itsd_unet_query)
   int* d_t = nullptr;
   int* d_nan = nullptr;
   RunParams* d_run = nullptr;
@@ -1349,6 +1360,9 @@ void drop_schedule(itsd_unet* u) {
   clear_graphs(u);
   u->trace = nullptr;
   u->trace_rows = u->trace_stride = 0;
+  u->guidance = 0;  // (the device buffers stay: no graph that reads them survives clear_graphs)
+  u->gw_rows_h.clear();
+  u->gw_img_h.clear();
   hipFree(u->coeff1); hipFree(u->coeff2); hipFree(u->sqrt_var); hipFree(u->xrow); hipFree(u->temb_table);
   u->coeff1 = u->coeff2 = u->sqrt_var = u->xrow = u->temb_table = nullptr;
   u->T_sched = 0;
@@ -1410,14 +1424,16 @@ int leave_stream(itsd_unet* u, hipStream_t cs) {
   return ITSD_OK;
 }
 
-// The step graph of (n, labels present, noise pointer, option generation, schedule form, trace pointer and stride):
+// The step graph of (n, labels present, noise pointer, option generation, schedule form, trace pointer and stride,
+// guidance table kind, cond-only program; keep: an entry the eviction passes over, the run's other graph):
 // the cached one, or one step of c (the program -- the trace's finalize launch rides behind the tail -- then the step
 // counter's decrement) captured on u->stream, instantiated and cached -- 4 entries, the oldest out. The trace is in the
 // key because its pointer is baked into the captured launches: a graph captured untraced is never replayed traced. A
 // failed capture is ended and its graph destroyed before the error is returned.
-int step_graph(itsd_unet* u, const RunCtx& c, int n, bool labels, const float* noise, hipGraphExec_t* exec) {
+int step_graph(itsd_unet* u, const RunCtx& c, int n, bool labels, const float* noise, hipGraphExec_t* exec,
+               bool cond_only = false, hipGraphExec_t keep = nullptr) {
   const auto key = std::make_tuple(n, labels, noise, itsd::g_option_gen, u->sched_form, (const double*)u->trace,
-                                   u->trace_stride);
+                                   u->trace_stride, u->guidance, cond_only);
   for (auto& g : u->graphs)
     if (g.key == key) { *exec = g.exec; return ITSD_OK; }
   hipStream_t s = u->stream;
@@ -1431,7 +1447,12 @@ int step_graph(itsd_unet* u, const RunCtx& c, int n, bool labels, const float* n
   e = hipGraphInstantiate(exec, graph, nullptr, nullptr, 0);
   hipGraphDestroy(graph);
   if (e != hipSuccess) return fail(ITSD_ERR_HIP, std::string("instantiate: ") + hipGetErrorString(e));
-  if (u->graphs.size() >= 4) { hipGraphExecDestroy(u->graphs.front().exec); u->graphs.erase(u->graphs.begin()); }
+  if (u->graphs.size() >= 4) {  // the oldest out, but never the graph this run is about to launch as well
+    auto old = u->graphs.begin();
+    if (keep && old->exec == keep) ++old;
+    hipGraphExecDestroy(old->exec);
+    u->graphs.erase(old);
+  }
   u->graphs.push_back({key, *exec});
   ++u->graph_captures;
   return ITSD_OK;
@@ -1564,6 +1585,7 @@ const Option kOptions[] = {
     {"attn_wide_nq", &g_attn_wide_nq, 0, 2, 0, "channel-split attention: query groups a block (0 auto, 1, 2)"},
     {"attn_cs", &g_attn_cs, 0, 8, kDiag, "attn_mfma_kernel output-channel slices: 0 auto, 1..8 forced"},
     {"attn_aq", &g_attn_aq, 0, 64, kDiag | kSet, "attn_mfma_kernel queries per block: 0 auto, 32, 64", {0, 32, 64, -1}},
+    {"cfg_skip", &g_cfg_skip, 0, 1, 0, "rows of a guidance table with w == 0 run the cond-only step program (batch n): 0 off (the doubled batch through the table), 1 on"},
     {"spin_bound", &g_spin_bound, 0, 0x7fffffff, 0, "diagnostic: polls before an in-kernel hand-off wait fails (shipped 1 << 22)"},
 };
 }  // namespace
@@ -1632,6 +1654,8 @@ int itsd_unet_query(const itsd_unet* u, const char* key, int64_t* value) {
   else if (!std::strcmp(key, "T_sched")) *value = u->T_sched;
   else if (!std::strcmp(key, "sched_form")) *value = u->sched_form;
   else if (!std::strcmp(key, "trace")) *value = u->trace ? 1 : 0;
+  else if (!std::strcmp(key, "guidance")) *value = u->guidance;
+  else if (!std::strcmp(key, "cond_only_steps")) *value = u->cond_only_steps;
   else if (!std::strcmp(key, "ws_bytes")) *value = (int64_t)u->ws_bytes;
   else if (!std::strcmp(key, "ops")) *value = (int64_t)u->ops.size();
   else if (!std::strcmp(key, "status")) {  // synchronous: the in-kernel hand-off status word of the last forward / run
@@ -1710,6 +1734,8 @@ int itsd_unet_destroy(itsd_unet* u) {
   hipFree(u->vd_xt);
   hipFree(u->vd_part);
   hipFree(u->tr_part);
+  hipFree(u->gw_rows_d);
+  hipFree(u->gw_img_d);
   if (u->stream) hipStreamDestroy(u->stream);
   if (u->ev_in) hipEventDestroy(u->ev_in);
   if (u->ev_out) hipEventDestroy(u->ev_out);
@@ -1832,6 +1858,59 @@ int itsd_set_schedule_x0_2m(itsd_unet* u, const itsd_x0_schedule* sc, const floa
   return install_x0_schedule(u, sc, cp, true, "itsd_set_schedule_x0_2m");
 }
 
+// The guidance table of the installed x0-form schedule: one weight a row, one multiplier a candidate image. Every
+// refusal comes before the first HIP call. The values go to handle-owned device buffers that keep their addresses
+// (the captured step graphs read them), behind whatever u->stream has queued -- a run already queued keeps the values
+// it was queued under -- and the call returns once they are there, so the host copies and the device's agree.
+int itsd_set_guidance(itsd_unet* u, const float* w_rows, int rows, const float* w_img, int n_img) {
+  const std::string who = "itsd_set_guidance: ";
+  if (!u) return fail(ITSD_ERR_INVALID, who + "null handle");
+  if (!u->cfg) return fail(ITSD_ERR_INVALID, who + "not a CFG UNet (nothing to guide)");
+  if (!u->T_sched || !u->sched_form)
+    return fail(ITSD_ERR_INVALID, who + "no x0-form schedule installed (itsd_set_schedule_x0 / _2m; the ancestral form "
+                                        "keeps its scalar w: ddim with steps = T, eta = 1 is its x0-form equivalent)");
+  if (!w_rows && !w_img) {  // detach: the graphs captured without a table are still cached under their own key
+    u->guidance = 0;
+    u->gw_rows_h.clear();
+    u->gw_img_h.clear();
+    return ITSD_OK;
+  }
+  if (w_rows && rows != u->T_sched)
+    return fail(ITSD_ERR_INVALID, who + "rows = " + std::to_string(rows) + " != T_sched = " + std::to_string(u->T_sched));
+  if (w_img && (n_img < 1 || n_img > u->d.max_batch))
+    return fail(ITSD_ERR_INVALID, who + "n_img = " + std::to_string(n_img) + " outside [1, max_batch=" +
+                                      std::to_string(u->d.max_batch) + "]");
+  for (int k = 0; w_rows && k < rows; ++k)
+    if (!std::isfinite(w_rows[k])) return fail(ITSD_ERR_INVALID, who + "w_rows[" + std::to_string(k) + "] is not finite");
+  for (int i = 0; w_img && i < n_img; ++i)
+    if (!std::isfinite(w_img[i])) return fail(ITSD_ERR_INVALID, who + "w_img[" + std::to_string(i) + "] is not finite");
+  if (tail_block_straddles(u->H, u->H, u->acts[u->tail_in].C) && u->tail_wmf == SIZE_MAX)
+    return fail(ITSD_ERR_INVALID, who + "no guidance table at this tail geometry (a 256-pixel block of the generic tail "
+                                        "kernel would straddle two images: H W % 256 != 0)");
+  const int K = u->T_sched;
+  std::vector<float> r(K, u->guide_w), m;
+  if (w_rows) r.assign(w_rows, w_rows + K);
+  if (w_img) m.assign(w_img, w_img + n_img);
+  HIPCHK(hipSetDevice(u->device));
+  if (K > u->gw_rows_cap) {  // (a larger schedule came with drop_schedule: no graph holds the old address)
+    hipFree(u->gw_rows_d);
+    u->gw_rows_d = nullptr;
+    u->gw_rows_cap = 0;
+    HIPCHK(hipMalloc(&u->gw_rows_d, (size_t)K * 4));
+    u->gw_rows_cap = K;
+  }
+  if (!u->gw_img_d) HIPCHK(hipMalloc(&u->gw_img_d, (size_t)u->d.max_batch * 4));
+  u->guidance = 0;  // (until both uploads are in place)
+  HIPCHK(hipMemcpyAsync(u->gw_rows_d, r.data(), (size_t)K * 4, hipMemcpyHostToDevice, u->stream));
+  if (!m.empty())
+    HIPCHK(hipMemcpyAsync(u->gw_img_d, m.data(), m.size() * 4, hipMemcpyHostToDevice, u->stream));
+  HIPCHK(hipStreamSynchronize(u->stream));
+  u->gw_rows_h.swap(r);
+  u->gw_img_h.swap(m);
+  u->guidance = u->gw_img_h.empty() ? 1 : 2;
+  return ITSD_OK;
+}
+
 int itsd_sampler_run(itsd_unet* u, float* x, const int32_t* labels, int n, int t_begin, int t_end, uint64_t seed,
                      int64_t noise_offset, const float* noise, uint32_t flags, void* stream) {
   if (!u || !x) return fail(ITSD_ERR_INVALID, "null argument");
@@ -1862,10 +1941,15 @@ int itsd_sampler_run(itsd_unet* u, float* x, const int32_t* labels, int n, int t
       return fail(ITSD_ERR_INVALID, "itsd_sampler_run: no score trace at this tail geometry (a 256-pixel block of the "
                                     "generic tail kernel would straddle two images: H W % 256 != 0)");
   }
+  if (u->guidance == 2 && n > (int)u->gw_img_h.size())  // (attached under this x0-form schedule: itsd_set_guidance)
+    return fail(ITSD_ERR_INVALID, "itsd_sampler_run: batch " + std::to_string(n) + " > the " +
+                                      std::to_string(u->gw_img_h.size()) + " per-image guidance multipliers installed "
+                                      "(itsd_set_guidance)");
   hipStream_t cs = (hipStream_t)stream;
   hipStream_t s = u->stream;
   CHK(enter_stream(u, cs));
   u->last_forward_n = 0;  // (the tail input is overwritten: itsd_unet_representation refuses until the next forward)
+  u->cond_only_steps = 0;
   const int clip_at = (flags & ITSD_RUN_CLIP) ? t_end : -1;
   const size_t xbytes = (size_t)n * 3 * u->H * u->H * 4;
   HIPCHK(hipMemcpyAsync(u->x_state, x, xbytes, hipMemcpyDeviceToDevice, s));
@@ -1890,6 +1974,20 @@ int itsd_sampler_run(itsd_unet* u, float* x, const int32_t* labels, int n, int t
     }
   }
   t.noise = noise; t.run = u->d_run; t.nan_flag = u->d_nan;
+  // Under a guidance table the guided program reads its weights from the device tables (the x0-form modes' second
+  // instantiations), and a row whose weight is 0 -- eps = eps_c exactly -- runs a second program, co: the n conditional
+  // images with their labels through the same step mode's unguided instantiation, as the forward program runs a CFG
+  // net. The host picks the program per row from its copy of the rows.
+  const auto cond_only = [&](int row) { return u->guidance && g_cfg_skip && u->gw_rows_h[row] == 0.0f; };
+  bool any_co = false, any_guided = false;
+  for (int row = t_end; row <= t_begin; ++row) (cond_only(row) ? any_co : any_guided) = true;
+  RunCtx co = c;
+  if (u->guidance) {
+    t.cfg = 2;
+    t.gw_rows = u->gw_rows_d;  // (in the storage of the ancestral sqrt_var, null under this form)
+    t.gw_img = u->guidance == 2 ? u->gw_img_d : nullptr;
+    co.nb = n; co.uncond_from = -1; co.tail.cfg = 0;
+  }
 
   RunParams rp{};
   rp.seed = seed; rp.noise_offset = noise_offset; rp.clip_at = clip_at;
@@ -1898,16 +1996,21 @@ int itsd_sampler_run(itsd_unet* u, float* x, const int32_t* labels, int n, int t
   HIPCHK(launch_run_begin(u->d_t, t_begin, u->d_nan, u->d_run, rp, s));
   const int steps = t_begin - t_end + 1;
   if (flags & ITSD_RUN_GRAPH) {
-    hipGraphExec_t exec = nullptr;
-    CHK(step_graph(u, c, n, labels != nullptr, noise, &exec));
-    for (int i = 0; i < steps; ++i) HIPCHK(hipGraphLaunch(exec, s));
+    hipGraphExec_t exec = nullptr, exec_co = nullptr;  // (both looked up before either is launched)
+    if (any_guided) CHK(step_graph(u, c, n, labels != nullptr, noise, &exec));
+    if (any_co) CHK(step_graph(u, co, n, labels != nullptr, noise, &exec_co, true, exec));
+    for (int i = 0; i < steps; ++i) HIPCHK(hipGraphLaunch(cond_only(t_begin - i) ? exec_co : exec, s));
   } else {
-    const std::vector<ConvLaunch> convs = resolve_program(u, c);  // (the steps differ in device state only)
+    // (the steps of one program differ in device state only)
+    const std::vector<ConvLaunch> convs = any_guided ? resolve_program(u, c) : std::vector<ConvLaunch>();
+    const std::vector<ConvLaunch> convs_co = any_co ? resolve_program(u, co) : std::vector<ConvLaunch>();
     for (int i = 0; i < steps; ++i) {
-      CHK(run_program(u, c, convs, s));
+      const bool skip = cond_only(t_begin - i);
+      CHK(run_program(u, skip ? co : c, skip ? convs_co : convs, s));
       HIPCHK(launch_add_int(u->d_t, -1, s));
     }
   }
+  for (int row = t_end; row <= t_begin; ++row) u->cond_only_steps += cond_only(row) ? 1 : 0;
   HIPCHK(hipMemcpyAsync(x, u->x_state, xbytes, hipMemcpyDeviceToDevice, s));
   CHK(leave_stream(u, cs));
   if (two_m) {  // what this run leaves, for a later ITSD_RUN_CONTINUE
@@ -1961,11 +2064,18 @@ int itsd_sampler_predict_x0(itsd_unet* u, const float* x, const int32_t* labels,
   CHK(check_batch(u, n));
   if (t < 0 || t >= u->T_sched)
     return fail(ITSD_ERR_INVALID, "step " + std::to_string(t) + " outside [0, T_sched=" + std::to_string(u->T_sched) + ")");
+  if (u->guidance == 2)
+    return fail(ITSD_ERR_INVALID, "itsd_sampler_predict_x0: per-image guidance multipliers are installed "
+                                  "(itsd_set_guidance); the x0 epilogue guides with one scalar");
   hipStream_t cs = (hipStream_t)stream;
   hipStream_t s = u->stream;
   CHK(enter_stream(u, cs));
   u->last_forward_n = 0;  // (the tail input is overwritten: itsd_unet_representation refuses until the next forward)
   RunCtx c = step_ctx(u, n, const_cast<float*>(x), labels);
+  if (u->guidance) {  // the row's weight as the scalar (host side only: kTailX0 is what it was)
+    c.tail.guide_w = u->gw_rows_h[t];
+    c.tail.guide_w1 = (float)(1.0 + (double)u->gw_rows_h[t]);
+  }
   c.tail.step_mode = kTailX0; c.tail.a0 = a0; c.tail.b0 = b0; c.tail.x0_out = x0;
   HIPCHK(launch_set_int(u->d_t, t, s));
   HIPCHK(hipMemsetAsync(u->d_nan + 1, 0, 4, s));  // this forward's hand-off status (itsd_unet_query "status")

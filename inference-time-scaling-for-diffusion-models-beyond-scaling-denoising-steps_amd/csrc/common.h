@@ -402,10 +402,20 @@ enum TailMode : int {
   kTailX0Step2MMom = 7,  // kTailX0Step2M plus the x0 moments of every image
 };
 // EPI, the tail kernels' template parameter: eps and step share instantiation 0 (a.step_mode tells them apart at
-// run time); every other mode has its own.
-constexpr int tail_epi(int mode) { return mode <= kTailStep ? 0 : mode - 1; }
+// run time); every other mode has its own. The four x0-form step modes have a second one each, EPI 7..10 (3, 5, 6, 7
+// in this order): the same mode guided from the device tables gw_rows / gw_img (TailArgs::cfg == 2,
+// itsd_set_guidance). They are instantiations of their own so that every other one keeps its code.
+constexpr int kTailEpiGw = 7;  // the first table-guided instantiation
+constexpr int kTailEpis = 11;
+constexpr bool tail_epi_gw(int epi) { return epi >= kTailEpiGw; }
+constexpr int tail_epi_base(int epi) { return epi < kTailEpiGw ? epi : epi == kTailEpiGw ? 2 : epi - 4; }
+constexpr int tail_epi(int mode, bool gw = false) {
+  return mode <= kTailStep ? 0 : !gw ? mode - 1 : mode == 3 ? kTailEpiGw : mode + 3;  // (gw: x0-form modes only)
+}
 // ... and back: the one mode of instantiation epi >= 1, eps or step for 0
-constexpr TailMode tail_epi_mode(int epi, bool step) { return epi ? TailMode(epi + 1) : step ? kTailStep : kTailEps; }
+constexpr TailMode tail_epi_mode(int epi, bool step) {
+  return epi ? TailMode(tail_epi_base(epi) + 1) : step ? kTailStep : kTailEps;
+}
 // what a mode does
 constexpr bool tail_reads_x(int mode) { return mode != kTailEps && mode != kTailSse; }
 constexpr bool tail_loads_row(int mode) {  // row *tsel of the schedule tables and the run's parameters
@@ -419,13 +429,20 @@ constexpr bool tail_2m(int mode) { return mode == kTailX0Step2M || mode == kTail
 constexpr bool tail_traced(int mode) { return mode == kTailX0StepMom || mode == kTailX0Step2MMom; }
 // the block statistics it ends in (tail_block_stats: 2 sums; 2 sums, min, max), 0 where it ends in none
 constexpr int tail_stats(int mode) { return mode == kTailSse ? 2 : tail_traced(mode) ? 4 : 0; }
+static_assert(tail_epi(kTailX0Step, true) == 7 && tail_epi(kTailX0StepMom, true) == 8 &&
+                  tail_epi(kTailX0Step2M, true) == 9 && tail_epi(kTailX0Step2MMom, true) == 10 &&
+                  tail_epi_mode(7, false) == kTailX0Step && tail_epi_mode(8, false) == kTailX0StepMom &&
+                  tail_epi_mode(9, false) == kTailX0Step2M && tail_epi_mode(10, false) == kTailX0Step2MMom &&
+                  tail_epi_mode(6, false) == kTailX0Step2MMom && tail_epi_mode(1, false) == kTailX0,
+              "the table-guided instantiations and their modes");
 
 struct TailArgs {
   const void* g;        // NHWC [nb][H][W][C] : silu(gn(h))
   const float* w;       // [3][C][3][3] fp32 (reference layout)
   const float* b;       // [3]
   int H, W, C, n;       // n = output images
-  int cfg;              // eps = (1+w) eps(img) - w eps(img+n)  (DiffusionCondition.py:85)
+  int cfg;              // eps = (1+w) eps(img) - w eps(img+n)  (DiffusionCondition.py:85): 1 w = guide_w; 2 (the x0-form
+                        // step modes only) w = gw_rows[*tsel] (* gw_img[img]), below
   float guide_w;        // w (fp32 cast of the Python float)
   float guide_w1;       // (1 + w) computed in double then cast, as the reference's scalar
   // mode
@@ -437,7 +454,9 @@ struct TailArgs {
   // of the first two: xcp, the sixth row table cp[K], and hist, the previous row's x0 NCHW fp32 [n][3][H][W])
   union { const float* coeff1; const float* xcp; };
   union { const float* coeff2; float* hist; };
-  const float* sqrt_var;
+  // (cfg == 2: gw_rows, the guidance weight of every row, device fp32 [T_sched], in the storage of the third ancestral
+  // table; and gw_img, the candidates' multipliers, device fp32 [n] or null = 1, in that of kTailX0's output)
+  union { const float* sqrt_var; const float* gw_rows; };
   const float* noise;   // [T][n][3][H][W] or null
   const RunParams* run; // seed / noise offset / clip step of this run (device)
   int* nan_flag;
@@ -449,7 +468,7 @@ struct TailArgs {
   const bf16_t* wmf;
   // kTailX0 (itsd_sampler_predict_x0): a0 = 1/sqrt(abar_t), b0 = sqrt(1/abar_t - 1) as fp32, output NCHW [n][3][H][W]
   float a0, b0;
-  float* x0_out;
+  union { float* x0_out; const float* gw_img; };
   // kTailX0Step (itsd_sampler_run under an x0-form schedule, itsd_set_schedule_x0): row k = *tsel of five device
   // tables [K] -- a0, b0, c0, cx, sg in this order -- and whether the x_0 estimate is clipped. tsel, noise (indexed by
   // row), run and nan_flag as in kTailStep; coeff1 / coeff2 / sqrt_var are not read
@@ -478,13 +497,18 @@ struct TailArgs {
   // correction  m = ((c0*x0) + (cp*x0p)) + (cx*x),  cp = xcp[*tsel], x0p = hist[o] (this row's own x0 where
   // *tsel == RunParams::restart_at); a row with cp == 0 is kTailX0Step's expression and does not read hist. Every
   // row stores its x0 to hist[o]. The Mom form adds this row's x0 (not the combination) to the moments.
+  // cfg == 2 (itsd_sampler_run with a guidance table attached, itsd_set_guidance; the four x0-form step modes, in
+  // instantiations of their own):  w = gw_rows[*tsel] ; if (gw_img) w = w * gw_img[img] ; w1 = 1.0f + w ;
+  // e = w1 * ec - w * eu  (fp32, no contraction: cfg == 1's expression and, for w == guide_w, its bits). img is the
+  // candidate, never img + n; a block lies in one image, so w sits in scalar registers.
 };
 static_assert(sizeof(TailArgs) == 240, "TailArgs is the tail kernels' argument block: a larger one changed the "
                                        "register allocation of the existing instantiations (DESIGN section 13)");
 static_assert(offsetof(TailArgs, xcp) == offsetof(TailArgs, coeff1) && offsetof(TailArgs, coeff1) == 80 &&
                   offsetof(TailArgs, hist) == offsetof(TailArgs, coeff2) && offsetof(TailArgs, coeff2) == 88 &&
-                  offsetof(TailArgs, sqrt_var) == 96,
-              "the 2M operands overlay the ancestral tables");
+                  offsetof(TailArgs, sqrt_var) == 96 && offsetof(TailArgs, gw_rows) == 96 &&
+                  offsetof(TailArgs, gw_img) == offsetof(TailArgs, x0_out),
+              "the 2M and guidance-table operands overlay the ancestral tables and kTailX0's output");
 
 constexpr int kBranchChunk = 256;  // parent-table rows a branch_kernel launch carries in its arguments (1 KiB)
 

@@ -1465,7 +1465,9 @@ __device__ __forceinline__ float philox_normal(unsigned long long seed, unsigned
 //   2M step + moments (kTailX0Step2MMom, its own instantiation)  the 2M step, bit-identical x and hist, and the
 //          moments of this row's own x0 (not of the combination) as in the x0 step + moments.
 // EPI, the kernels' template parameter, names the instantiation (tail_epi of common.h): 0 eps / step, 1 x0, 2 x0 step,
-// 3 sse, 4 x0 step + moments, 5 2M step, 6 2M step + moments. Each kernel ends in one loop over its output items, which
+// 3 sse, 4 x0 step + moments, 5 2M step, 6 2M step + moments, 7..10 the four x0-form steps guided from the device
+// tables (TailArgs::cfg == 2: w = gw_rows[k] (* gw_img[img]), w1 = 1.0f + w, eps = w1 eps_c - w eps_u; the step after
+// it is the mode's own, so with gw_rows[k] == guide_w and no multipliers these are the scalar path's bits). Each kernel ends in one loop over its output items, which
 // calls tail_item, and one call of tail_block_stats, which every thread of the block reaches and which is empty where
 // the mode ends in no statistics.
 __device__ __forceinline__ float tail_x0(float a0, float b0, float xv, float e) {
@@ -1498,9 +1500,17 @@ struct TailStep2M : TailStep {
   float cp = 0.f;       // the row's weight of the previous row's x0
   int restart_at = -1;  // RunParams::restart_at
 };
-template <int EPI> using TailStepOf = std::conditional_t<tail_2m(kTailMode<EPI>), TailStep2M, TailStep>;
+// ... and the table-guided instantiations (EPI 7..10) their image's guidance weight w and w1 = 1.0f + w, again in a type
+// only they see: loaded with the row's other scalars, at the kernel's top, so that they are scalar loads
+template <typename Base> struct TailStepGw : Base {
+  float gw = 0.f, gw1 = 1.f;
+};
+template <int EPI> using TailStepBase = std::conditional_t<tail_2m(kTailMode<EPI>), TailStep2M, TailStep>;
 template <int EPI>
-__device__ __forceinline__ TailStepOf<EPI> tail_step_load(const TailArgs& a) {
+using TailStepOf = std::conditional_t<tail_epi_gw(EPI), TailStepGw<TailStepBase<EPI>>, TailStepBase<EPI>>;
+// img: the block's image (read by the table-guided instantiations only; their blocks lie in one image)
+template <int EPI>
+__device__ __forceinline__ TailStepOf<EPI> tail_step_load(const TailArgs& a, int img = 0) {
   TailStepOf<EPI> s;
   if (tail_loads_row(tail_mode<EPI>(a))) {
     s.t = *a.tsel;
@@ -1516,6 +1526,13 @@ __device__ __forceinline__ TailStepOf<EPI> tail_step_load(const TailArgs& a) {
       if constexpr (tail_2m(kTailMode<EPI>)) {
         s.cp = a.xcp[s.t];
         s.restart_at = a.run->restart_at;
+      }
+      if constexpr (tail_epi_gw(EPI)) {  // the row's weight times the candidate's multiplier
+#pragma clang fp contract(off)
+        float w = a.gw_rows[s.t];
+        if (a.gw_img) w = w * a.gw_img[__builtin_amdgcn_readfirstlane(img)];
+        s.gw = w;
+        s.gw1 = 1.0f + w;
       }
     } else {
       s.c1 = a.coeff1[s.t];
@@ -1641,7 +1658,11 @@ __device__ __forceinline__ bool tail_item(const TailArgs& a, const TailStepOf<EP
     if (a.cfg) {
 #pragma clang fp contract(off)
       const float u = eu();
-      e = a.guide_w1 * e - a.guide_w * u;
+      if constexpr (tail_epi_gw(EPI)) {
+        e = s.gw1 * e - s.gw * u;  // (tail_step_load: the image's weight from the tables)
+      } else {
+        e = a.guide_w1 * e - a.guide_w * u;
+      }
     }
     return tail_finish<EPI>(a, s, o, xv, e, mom);
   }
@@ -1738,7 +1759,7 @@ __global__ __launch_bounds__(256) void tail_kernel(TailArgs a) {
   float eps[3], u[3] = {0.f, 0.f, 0.f};
   conv3(img, eps[0], eps[1], eps[2]);
   if (a.cfg) conv3(img + a.n, u[0], u[1], u[2]);
-  const TailStepOf<EPI> st = tail_step_load<EPI>(a);
+  const TailStepOf<EPI> st = tail_step_load<EPI>(a, img);
   TailMom mom;
   bool bad = false;
 #pragma unroll
@@ -1767,6 +1788,10 @@ __global__ __launch_bounds__(256) void tail2_kernel(TailArgs a) {
   tail_stage_weights(wl, a.w, C);
   const int bpi = H / rpb;
   const int img = blockIdx.x / bpi, y0 = (blockIdx.x % bpi) * rpb;
+  // (the table-guided instantiations load the step's scalars here, ahead of the barriers, as scalar loads; the others
+  // where they always did, beside their item)
+  TailStepOf<EPI> st_top;
+  if constexpr (tail_epi_gw(EPI)) st_top = tail_step_load<EPI>(a, img);
   // wave = channel quarter (its weight reads are wave-uniform LDS broadcasts),
   // lane = output pixel (halo reads at a conflict-free padded pixel stride)
   const int tid = threadIdx.x, pl = tid & 63, cq = tid >> 6;
@@ -1822,7 +1847,11 @@ __global__ __launch_bounds__(256) void tail2_kernel(TailArgs a) {
       return a.b[oc] + s;
     };
     const size_t o = tail_offset(img, y0, opx, oc, H, W);
-    if (tail_item<EPI>(a, tail_step_load<EPI>(a), o, img, tail_x<EPI>(a, o), e(0), [&] { return e(1); }, mom))
+    const auto step = [&] {
+      if constexpr (tail_epi_gw(EPI)) return st_top;
+      else return tail_step_load<EPI>(a, img);
+    };
+    if (tail_item<EPI>(a, step(), o, img, tail_x<EPI>(a, o), e(0), [&] { return e(1); }, mom))
       atomicOr(a.nan_flag, 1);
   }
   tail_block_stats<4, tail_stats(kTailMode<EPI>)>(a, wl, mom);
@@ -1873,7 +1902,7 @@ __global__ __launch_bounds__(NTH, 2) void tail_mfma_kernel(TailArgs a) {
   float xpre[TIT] = {};
   TailStepOf<EPI> st;
   if (tail_reads_x(tail_mode<EPI>(a))) {
-    st = tail_step_load<EPI>(a);
+    st = tail_step_load<EPI>(a, img);
 #pragma unroll
     for (int k = 0; k < TIT; ++k) {
       const int it = tid + NTH * k, opx = it < TM_PX * 3 ? it / 3 : 0, oc = it < TM_PX * 3 ? it - opx * 3 : 0;
@@ -2012,9 +2041,11 @@ __global__ __launch_bounds__(64) void tail_stats_finalize_kernel(const float* pa
 
 // kTailX0 needs its operands (and nothing of the step's); the x0-form step its tables and the step's run state;
 // kTailSse its two outputs; the Mom modes what their step needs and a trace that holds the batch; the 2M modes the
-// x0-form step's operands, the cp table and the history
+// x0-form step's operands, the cp table and the history; the guidance tables (cfg == 2) an x0-form step and the row
+// table
 static bool tail_x0_ok(const TailArgs& a) {
   if (a.step_mode < kTailEps || a.step_mode > kTailX0Step2MMom) return false;
+  if (a.cfg < 0 || a.cfg > 2 || (a.cfg == 2 && !(tail_x0_form(a.step_mode) && a.gw_rows))) return false;
   if (a.step_mode == kTailSse) return a.vpart && a.vsse;
   if (tail_2m(a.step_mode) && !(a.xcp && a.hist)) return false;
   if (tail_traced(a.step_mode) && !(a.tpart && a.trace && a.trace_rows >= 1 && a.trace_stride >= a.n))
@@ -2036,16 +2067,18 @@ template <int E> using TailEpi = std::integral_constant<int, E>;
 // text, and the census and the profiles key on that of the forward and the ancestral step). BIG: all of them may use up
 // to kTailSmemMax of dynamic shared memory; the attribute is set once. PXB: the pixels of a block. The modes that end
 // in statistics are followed by their finalize launch, and are refused where a block would straddle two images (an
-// image is not a whole number of blocks).
+// image is not a whole number of blocks); so are the table-guided instantiations (cfg == 2: EPI 7..10), whose weight
+// is one image's.
 #define ITSD_RETURN_TAIL_LAUNCH(PLAIN, FAMILY, BIG, PXB, grid, block, sm, s, a)                                      \
   do {                                                                                                               \
     const auto member = [](auto epi) -> TailKernel {                                                                 \
       constexpr int E = decltype(epi)::value;                                                                        \
       return FAMILY;                                                                                                 \
     };                                                                                                               \
-    const TailKernel kern[] = {member(TailEpi<0>{}), member(TailEpi<1>{}), member(TailEpi<2>{}),                     \
-                               member(TailEpi<3>{}), member(TailEpi<4>{}), member(TailEpi<5>{}),                     \
-                               member(TailEpi<6>{})};                                                                \
+    const TailKernel kern[kTailEpis] = {member(TailEpi<0>{}), member(TailEpi<1>{}), member(TailEpi<2>{}),            \
+                                        member(TailEpi<3>{}), member(TailEpi<4>{}), member(TailEpi<5>{}),            \
+                                        member(TailEpi<6>{}), member(TailEpi<7>{}), member(TailEpi<8>{}),            \
+                                        member(TailEpi<9>{}), member(TailEpi<10>{})};                                \
     static bool attr = !(BIG);                                                                                       \
     if (!attr) {                                                                                                     \
       for (const TailKernel f : kern) {                                                                              \
@@ -2055,8 +2088,9 @@ template <int E> using TailEpi = std::integral_constant<int, E>;
       }                                                                                                              \
       attr = true;                                                                                                   \
     }                                                                                                                \
-    const int epi = tail_epi((a).step_mode), nst = tail_stats((a).step_mode);                                        \
-    if (nst && ((a).n < 1 || ((a).H * (a).W) % (PXB))) return hipErrorInvalidValue;                                  \
+    const bool gw = (a).cfg == 2;                                                                                    \
+    const int epi = tail_epi((a).step_mode, gw), nst = tail_stats((a).step_mode);                                    \
+    if ((nst || gw) && ((a).n < 1 || ((a).H * (a).W) % (PXB))) return hipErrorInvalidValue;                          \
     if (epi == 0) ITSD_LAUNCH(PLAIN, grid, block, sm, s, a);                                                         \
     else ITSD_LAUNCH(kern[epi], grid, block, sm, s, a);                                                              \
     if (nst) {                                                                                                       \

@@ -24,6 +24,11 @@ is available by passing ``noise=`` (see ``reference_noise_plan``).
 with the previous row's x_0 estimate kept inside the library (``schedule.x0_2m_rows``, ``itsd_set_schedule_x0_2m``).
 A ``run`` starts first order at its top row unless ``cont=True`` continues the run before it. Everything else is as
 under ddim: ``X0_FORM`` names the two.
+
+Guidance schedules (the conditional sampler under ddim / dpmpp2m): ``guidance=`` a weight for every row
+(``schedule.guidance_rows``) and ``run(.., guidance_scale=)`` a multiplier for every image, both read on the device
+(``itsd_set_guidance``) under the one captured step graph; a row whose weight is 0 runs the cond-only step, half the
+UNet batch. ``unet_evals_per_image`` counts what a run costs.
 """
 from __future__ import annotations
 
@@ -50,7 +55,10 @@ def _draw_seed() -> int:
 
 class GaussianDiffusionSampler:
     def __init__(self, model, beta_1: float, beta_T: float, T: int, w: float = 0.0, *, sampler: str = "ddpm",
-                 steps=None, eta: float = 0.0, clip_x0: bool = False):
+                 steps=None, eta: float = 0.0, clip_x0: bool = False, guidance=None):
+        if guidance is not None and not isinstance(self, CondGaussianDiffusionSampler):
+            raise ValueError("guidance= belongs to the conditional sampler (CondGaussianDiffusionSampler): the "
+                             "unconditional model has nothing to guide")
         self.model = model
         self.T = int(T)
         self.w = float(w)
@@ -81,6 +89,9 @@ class GaussianDiffusionSampler:
         elif steps is not None or eta != 0.0 or clip_x0:
             raise ValueError("steps, eta and clip_x0 belong to sampler='ddim' / 'dpmpp2m'")
         self.last_seed = None  # Philox key of the last run (set by run)
+        self.guidance = None  # the row table of the conditional sampler (CondGaussianDiffusionSampler)
+        self.last_cond_only_steps = 0  # rows of the last run that ran the cond-only step
+        self.last_unet_evals_per_image = 0  # UNet evaluations an image of the last run cost
 
     @property
     def x0_form(self) -> bool:
@@ -107,13 +118,43 @@ class GaussianDiffusionSampler:
     def eval(self):
         return self
 
-    def _native(self, n: int):
+    def _native(self, n: int, guidance_scale: Optional[torch.Tensor] = None):
         nat = self.model.native(n)
         if getattr(nat, "_sched_args", None) is not self._sched_args:
             install = {"ddpm": nat.set_schedule, "ddim": nat.set_schedule_x0, "dpmpp2m": nat.set_schedule_x0_2m}
             install[self.sampler](*self._sched_args)
             nat._sched_args = self._sched_args
+            nat._guidance = None  # (installing a schedule detaches the table)
+        self._install_guidance(nat, guidance_scale)
         return nat
+
+    def _install_guidance(self, nat, scale: Optional[torch.Tensor]) -> None:
+        """Bring the handle's guidance table to (this sampler's rows, ``scale``): installed when either differs from
+        what the handle holds -- after every schedule install, so two samplers on one handle each run their own --
+        and detached when this sampler has neither."""
+        want = None
+        if self.guidance is not None or scale is not None:
+            want = (self.guidance, None if scale is None else tuple(scale.tolist()))
+        have = getattr(nat, "_guidance", None)
+        if (want is None and have is None) or (want is not None and have is not None and want[0] is have[0]
+                                               and want[1] == have[1]):
+            return  # (the rows by identity: set_guidance makes a new tensor)
+        if want is None:
+            nat.set_guidance(None, None)
+        else:
+            nat.set_guidance(self.guidance, scale)
+        nat._guidance = want
+
+    def unet_evals_per_image(self, t_begin: Optional[int] = None, t_end: int = 0) -> int:
+        """UNet evaluations one image costs over rows t_begin..t_end: 2 a guided row (cond and uncond), 1 a cond-only
+        row (a guidance row of weight 0) and 1 a row of the unconditional sampler."""
+        t_begin = self.n_steps - 1 if t_begin is None else int(t_begin)
+        rows = range(int(t_end), t_begin + 1)
+        if not getattr(self.model.arch, "cfg", False):
+            return len(rows)
+        if self.guidance is None:
+            return 2 * len(rows)
+        return sum(1 if float(self.guidance[k]) == 0.0 else 2 for k in rows)
 
     # --- reference API
     def predict_xt_prev_mean_from_eps(self, x_t, t, eps):
@@ -148,12 +189,16 @@ class GaussianDiffusionSampler:
 
     def run(self, x: torch.Tensor, t_begin: Optional[int] = None, t_end: int = 0, labels=None, seed=None,
             noise: Optional[torch.Tensor] = None, noise_offset: int = 0, graph: bool = True, clip=None,
-            sync: bool = True, trace: Optional[torch.Tensor] = None, cont: bool = False) -> torch.Tensor:
+            sync: bool = True, trace: Optional[torch.Tensor] = None, cont: bool = False,
+            guidance_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
         """In-place steps t_begin..t_end on a contiguous fp32 device tensor x (rows of the schedule: timesteps for
         ddpm). ``trace`` (``new_trace``; ddim / dpmpp2m only) is attached for this call and detached after it: x is the
         untraced run's bit for bit, and trace[k, :len(x)] holds the x_0 moments of every row k run. ``cont`` (dpmpp2m
         only; ``ITSD_RUN_CONTINUE``): the step at t_begin is second order on the x_0 the previous run left at row
-        t_begin + 1 for the same batch; without it a run's first step is first order."""
+        t_begin + 1 for the same batch; without it a run's first step is first order. ``guidance_scale`` (the
+        conditional sampler under ddim / dpmpp2m): one multiplier of the row's guidance weight for each image of x."""
+        if guidance_scale is not None:
+            guidance_scale = self._check_guidance_scale(guidance_scale, x.shape[0])
         if trace is not None and not self.x0_form:
             raise ValueError("run(trace=) needs sampler='ddim' or 'dpmpp2m': the ancestral step has no x_0 rows")
         t_begin = self.n_steps - 1 if t_begin is None else int(t_begin)
@@ -168,10 +213,11 @@ class GaussianDiffusionSampler:
                 raise ValueError("noise must be [T, *x.shape] indexed by step t")
         if labels is not None:
             labels = labels.flatten().to(x.device, torch.int32).contiguous()
-        nat = self._native(x.shape[0])
+        nat = self._native(x.shape[0], guidance_scale)
         if trace is None:
             nat.run(x, t_begin, t_end, seed or 0, noise=noise, labels=labels, noise_offset=noise_offset, graph=graph,
                     clip=clip, sync=sync, cont=cont)
+            self._count_evals(nat, t_begin - t_end + 1)
             return x
         nat.set_trace(trace)
         try:
@@ -179,7 +225,17 @@ class GaussianDiffusionSampler:
                     clip=clip, sync=sync, cont=cont)
         finally:  # (host state: steps already queued keep the pointer their launches were given)
             nat.set_trace(None)
+        self._count_evals(nat, t_begin - t_end + 1)
         return x
+
+    def _check_guidance_scale(self, scale, n: int) -> torch.Tensor:
+        raise ValueError("guidance_scale belongs to the conditional sampler (CondGaussianDiffusionSampler)")
+
+    def _count_evals(self, nat, steps: int) -> None:
+        """What the run just queued cost an image: the library's count of its cond-only steps decides."""
+        self.last_cond_only_steps = nat.query("cond_only_steps") if self.guidance is not None else 0
+        per_row = 2 if getattr(self.model.arch, "cfg", False) else 1
+        self.last_unet_evals_per_image = per_row * steps - self.last_cond_only_steps
 
     def predict_x0(self, x: torch.Tensor, t: int, labels: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The x_0 estimate of a half-denoised state: x is x_t, the input of step t (what ``run(.., t_end=t + 1)``
@@ -235,8 +291,37 @@ class GaussianDiffusionSampler:
 class CondGaussianDiffusionSampler(GaussianDiffusionSampler):
     """``DiffusionCondition.py:56``: guided eps = (1+w) eps(x,t,y) - w eps(x,t,0)."""
 
-    def __init__(self, model, beta_1: float, beta_T: float, T: int, w: float = 0.0, **kw):
+    def __init__(self, model, beta_1: float, beta_T: float, T: int, w: float = 0.0, *, guidance=None, **kw):
+        """``guidance``: the guidance weight of every row, [n_steps] (``schedule.guidance_rows``); None keeps the
+        scalar w on every row. ddim / dpmpp2m only: the ancestral step keeps its scalar."""
         super().__init__(model, beta_1, beta_T, T, w, **kw)
+        self.set_guidance(guidance)
+
+    def set_guidance(self, guidance) -> None:
+        """Replace the row table (None: back to the scalar w on every row). The schedule stays installed, so the next
+        run uploads new values under the step graphs already captured."""
+        if guidance is None:
+            self.guidance = None
+            return
+        if not self.x0_form:
+            raise ValueError("guidance= needs sampler='ddim' or 'dpmpp2m': the ancestral step keeps its scalar w "
+                             "(ddim with steps=T, eta=1 is its x0-form equivalent)")
+        g = torch.as_tensor(guidance).detach().to("cpu", torch.float32).flatten().contiguous().clone()
+        if g.numel() != self.n_steps:
+            raise ValueError(f"guidance has {g.numel()} rows, the sampler walks {self.n_steps}")
+        if not bool(torch.isfinite(g).all()):
+            raise ValueError("guidance holds a non-finite weight")
+        self.guidance = g
+
+    def _check_guidance_scale(self, scale, n: int) -> torch.Tensor:
+        if not self.x0_form:
+            raise ValueError("guidance_scale needs sampler='ddim' or 'dpmpp2m': the ancestral step keeps its scalar w")
+        s = torch.as_tensor(scale).detach().to("cpu", torch.float32).flatten().contiguous()
+        if s.numel() != int(n):
+            raise ValueError(f"guidance_scale has {s.numel()} entries for {int(n)} images")
+        if not bool(torch.isfinite(s).all()):
+            raise ValueError("guidance_scale holds a non-finite multiplier")
+        return s
 
     def forward(self, x_T: torch.Tensor, labels: torch.Tensor, noise: Optional[torch.Tensor] = None,
                 seed: Optional[int] = None, graph: bool = True) -> torch.Tensor:

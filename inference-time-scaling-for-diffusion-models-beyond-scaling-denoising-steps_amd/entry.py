@@ -74,6 +74,22 @@ Keys beyond the reference (all optional):
   ``injection_step`` / ``renoise_steps`` count rows. ``sampler.steps=20`` overrides work
   as for ``search.*``.
 
+* ``guidance``: a top-level block of the conditional eval (``MainCondition.py``) under ``sampler.kind: ddim | dpmpp2m``
+  (no reference counterpart: the reference guides every step with the one scalar ``w``): the guidance weight as a
+  function of the row, read on the device under the one captured step graph (``schedule.guidance_rows``, DESIGN.md
+  section 15). A row of weight 0 runs the cond-only step, half the UNet batch::
+
+      guidance:
+        kind: interval           # constant | interval | linear | table
+        t_lo: 200                # interval: w where t_lo <= timestep <= t_hi, else 0
+        t_hi: 800
+        # linear: w_top (the first, noisiest row) and w_end (the last row); table: values, one number a row
+
+  ``search.guidance_scales: [0.5, 1.0, 1.5]`` deals every candidate of a round a multiplier of that weight, round
+  robin by its global index (random -- then run with the eval's labels --, zero_order and placeholder path search);
+  the history reports ``guidance_scales`` and ``best_guidance_scale``. The result and the search's JSON report
+  ``unet_evals_per_image``: 2 a guided row, 1 a cond-only row. Every bad value raises a ValueError naming its key.
+
 There is no training entry: ``state: train`` raises (training is out of scope).
 """
 from __future__ import annotations
@@ -457,6 +473,42 @@ def sampler_kwargs(cfg: Dict[str, Any], T: int) -> Dict[str, Any]:
     return {"sampler": kind, "steps": steps, "eta": float(eta), "clip_x0": clip}
 
 
+def guidance_args(cfg: Dict[str, Any], T: int, condition: bool = True) -> Dict[str, Any]:
+    """The top-level ``guidance:`` block (``kind: constant | interval | linear | table`` plus that kind's keys:
+    ``t_lo`` / ``t_hi``, ``w_top`` / ``w_end``, ``values``; ``schedule.guidance_rows``) and ``search.guidance_scales``
+    (finite numbers >= 0, one multiplier a candidate, dealt round robin) as {"guidance": the row table or None,
+    "guidance_scales": the list or None}. Both belong to the conditional eval (MainCondition.py) under
+    ``sampler.kind: ddim | dpmpp2m``; every bad value raises a ValueError naming its key."""
+    from .schedule import guidance_rows, strided_timesteps
+
+    g = cfg.get("guidance")
+    scales = (cfg.get("search") or {}).get("guidance_scales")
+    out: Dict[str, Any] = {"guidance": None, "guidance_scales": None}
+    if g is None and scales is None:
+        return out
+    key = "guidance" if g is not None else "search.guidance_scales"
+    if not condition:
+        raise ValueError(f"{key} belongs to the conditional eval (MainCondition.py): the unconditional model has "
+                         "nothing to guide")
+    kw = sampler_kwargs(cfg, T)
+    if kw.get("sampler") not in ("ddim", "dpmpp2m"):
+        raise ValueError(f"{key} needs sampler.kind: ddim | dpmpp2m (the ancestral step, ddpm, keeps its scalar w; "
+                         "ddim with steps = T, eta = 1 is its x0-form equivalent)")
+    if scales is not None:
+        ok = isinstance(scales, (list, tuple)) and len(scales) > 0 and all(
+            isinstance(v, (int, float)) and not isinstance(v, bool) and v == v and abs(v) != float("inf") and v >= 0
+            for v in scales)
+        if not ok:
+            raise ValueError(f"search.guidance_scales = {scales!r} must be a non-empty list of finite numbers >= 0")
+        out["guidance_scales"] = [float(v) for v in scales]
+    if g is not None:
+        if not isinstance(g, dict):
+            raise ValueError("guidance must be a block (kind plus that kind's keys)")
+        tau = strided_timesteps(int(T), int(T) if kw["steps"] is None else int(kw["steps"]))
+        out["guidance"] = guidance_rows(tau, cfg.get("w", 0.0), g)  # (its errors name guidance.<key>)
+    return out
+
+
 def search_verifier(s: Dict[str, Any], sampler, has_labels: bool):
     """The ``search`` block's verifier object. ``denoise`` / ``class`` build a ``DenoisingVerifier`` over the round's
     own sampler from ``verifier_probes`` (an int, or a list of rows) and ``verifier_seed``; every bad value raises a
@@ -533,7 +585,8 @@ def particle_args(cfg: Dict[str, Any], T: int) -> Dict[str, Any]:
             "lam": float(lam), "potential": pot}
 
 
-def _search(cfg: Dict[str, Any], sampler, img_size: int, labels: Optional[torch.Tensor]) -> Optional[Dict[str, Any]]:
+def _search(cfg: Dict[str, Any], sampler, img_size: int, labels: Optional[torch.Tensor],
+            guidance_scales: Optional[Sequence[float]] = None) -> Optional[Dict[str, Any]]:
     s = cfg.get("search") or {}
     algo = (s.get("algorithm") or "none").lower()
     if algo == "none":
@@ -549,12 +602,20 @@ def _search(cfg: Dict[str, Any], sampler, img_size: int, labels: Optional[torch.
         # verifier.py:243-246 averages the off-diagonal of the in-batch Gram matrix: one image
         # per candidate has none, every score is NaN and the reference search never picks one
         raise ValueError("search.verifier selfsup needs search.batch_per_candidate >= 2")
-    eng = SearchEngine(sampler, ver, seed=int(cfg.get("seed") or 0))
+    if guidance_scales is not None:  # (an engine without them is built as it always was)
+        if algo in ("gradient", "particle") or (algo == "path" and (s.get("path_mode") or "").lower() == "branch"):
+            raise ValueError(f"search.guidance_scales: search.algorithm {algo} does not run per-candidate guidance "
+                             "(random | zero_order | path with path_mode placeholder)")
+        eng = SearchEngine(sampler, ver, seed=int(cfg.get("seed") or 0), guidance_scales=guidance_scales)
+    else:
+        eng = SearchEngine(sampler, ver, seed=int(cfg.get("seed") or 0))
     lab = None if labels is None else labels[:shape[0]]
     if algo == "random":
-        if lab is not None:
+        if lab is not None and guidance_scales is None:
             raise ValueError("search.algorithm random is unconditional (search_algorithm.py:33-83)")
-        best, score, hist = eng.random_search(int(s.get("n_candidates") or 4), shape)
+        # (a sweep over guidance scales is conditional by nature: the round then carries the labels)
+        best, score, hist = eng.random_search(int(s.get("n_candidates") or 4), shape,
+                                              **({} if lab is None else {"labels": lab}))
     else:
         init = eng.initial_noise(shape)  # the same pivot on every rank (Philox of the seed)
         if algo == "zero_order":
@@ -592,6 +653,8 @@ def _search(cfg: Dict[str, Any], sampler, img_size: int, labels: Optional[torch.
     # once at the end -- the exact trajectory that earned best_score (not a re-run)
     x = eng.best_image
     out = {"algorithm": algo, "best_score": score, "nfes": eng.nfes, "history": hist}
+    if hasattr(sampler, "last_unet_evals_per_image"):  # of the search's last round
+        out["unet_evals_per_image"] = int(sampler.last_unet_evals_per_image)
     if eng.rank == 0 and x is not None:
         d = _out_dir(cfg)
         name = s.get("bestImgName") or "SearchBestImgs.png"
@@ -672,10 +735,12 @@ def eval_condition(cfg: Dict[str, Any]) -> Dict[str, Any]:
     with torch.no_grad():
         labels = cfg_eval_labels(int(cfg["batch_size"]))
         print("labels: ", labels)
+        ga = guidance_args(cfg, cfg["T"])  # (checked before the model is built)
         model = build_cfg_model(cfg)
         labels = labels.to(model.device)
+        gkw = {} if ga["guidance"] is None else {"guidance": ga["guidance"]}
         sampler = CondGaussianDiffusionSampler(model, cfg["beta_1"], cfg["beta_T"], cfg["T"], w=cfg["w"],
-                                               **sampler_kwargs(cfg, cfg["T"]))
+                                               **sampler_kwargs(cfg, cfg["T"]), **gkw)
         img = int(cfg["img_size"])
         noisy = torch.randn(size=[cfg["batch_size"], 3, img, img], device=model.device)
         imgs = _sample_sharded(sampler, noisy, labels) * 0.5 + 0.5
@@ -684,8 +749,9 @@ def eval_condition(cfg: Dict[str, Any]) -> Dict[str, Any]:
             save_image(torch.clamp(noisy * 0.5 + 0.5, 0, 1), os.path.join(d, cfg["sampledNoisyImgName"]),
                        nrow=cfg["nrow"])
             save_image(imgs, os.path.join(d, cfg["sampledImgName"]), nrow=cfg["nrow"])
-        res = {"noisy": noisy, "sampled": imgs, "labels": labels, "sampler_seed": sampler.last_seed}
-        res["search"] = _search(cfg, sampler, img, labels)
+        res = {"noisy": noisy, "sampled": imgs, "labels": labels, "sampler_seed": sampler.last_seed,
+               "unet_evals_per_image": int(sampler.last_unet_evals_per_image)}
+        res["search"] = _search(cfg, sampler, img, labels, guidance_scales=ga["guidance_scales"])
     return res
 
 
@@ -752,6 +818,8 @@ def _maybe_init_dist(cfg: Dict[str, Any]) -> None:
 def run(cfg: Dict[str, Any], condition: bool = False) -> Dict[str, Any]:
     if cfg.get("state", "eval") == "train":
         raise NotImplementedError("itsd is inference-only: training (Train.py:train) is out of scope; use state=eval")
+    if not condition:
+        guidance_args(cfg, int(cfg.get("T") or 1), condition=False)  # (refuses the conditional eval's keys)
     _maybe_init_dist(cfg)
     if condition:
         return eval_condition(cfg)

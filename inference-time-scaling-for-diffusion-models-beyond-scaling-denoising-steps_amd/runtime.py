@@ -95,6 +95,7 @@ _SIGS = {
                           ctypes.c_float],
     "itsd_set_schedule_x0": [ctypes.c_void_p, ctypes.POINTER(X0Schedule)],
     "itsd_set_schedule_x0_2m": [ctypes.c_void_p, ctypes.POINTER(X0Schedule), ctypes.c_void_p],
+    "itsd_set_guidance": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int],
     "itsd_sampler_run": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                          ctypes.c_uint64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p],
     "itsd_sampler_set_trace": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int],
@@ -282,6 +283,15 @@ class NativeUNet:
     def set_schedule_x0_2m(self, tau: Sequence[int], rows: Dict[str, torch.Tensor], clip_x0: bool, w: float = 0.0):
         self.set_schedule_x0(tau, rows, clip_x0, w, two_m=True)
 
+    def set_guidance(self, w_rows: Optional[torch.Tensor] = None, w_img: Optional[torch.Tensor] = None) -> None:
+        """Attach a guidance table to the installed x0-form schedule (``itsd_set_guidance``): ``w_rows`` one weight a
+        row (``schedule.guidance_rows``; None = the schedule's scalar), ``w_img`` one multiplier a candidate image
+        (None = 1). Both None detaches. Values are cast to fp32 and copied; installing a schedule detaches."""
+        r = None if w_rows is None else torch.as_tensor(w_rows).detach().to("cpu", torch.float32).contiguous().reshape(-1)
+        m = None if w_img is None else torch.as_tensor(w_img).detach().to("cpu", torch.float32).contiguous().reshape(-1)
+        check(lib().itsd_set_guidance(self.h, _ptr(r), 0 if r is None else r.numel(), _ptr(m),
+                                      0 if m is None else m.numel()))
+
     def run(self, x: torch.Tensor, t_begin: int, t_end: int, seed: int, noise: Optional[torch.Tensor] = None,
             labels: Optional[torch.Tensor] = None, noise_offset: int = 0, graph: bool = True, clip: bool = True,
             sync: bool = True, cont: bool = False) -> None:
@@ -333,7 +343,8 @@ class NativeUNet:
         return sse
 
     def query(self, key: str) -> int:
-        """itsd_unet_query: "graph_captures", "max_batch", "T_sched", "sched_form", "trace", "ws_bytes", "ops"."""
+        """itsd_unet_query: "graph_captures", "max_batch", "T_sched", "sched_form", "trace", "guidance", "cond_only_steps",
+        "ws_bytes", "ops"."""
         v = ctypes.c_int64()
         check(lib().itsd_unet_query(self.h, key.encode(), ctypes.byref(v)))
         return int(v.value)

@@ -156,3 +156,63 @@ def x0_2m_rows(alphas_bar: torch.Tensor, tau: Sequence[int]) -> Dict[str, torch.
     rows["c0"] = c0
     rows["cp"] = cp
     return rows
+
+
+GUIDANCE_KINDS = ("constant", "interval", "linear", "table")
+
+
+def _finite(name: str, v) -> float:
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(float(v)):
+        raise ValueError(f"{name} = {v!r} must be a finite number")
+    return float(v)
+
+
+def guidance_rows(tau: Sequence[int], w: float, spec) -> torch.Tensor:
+    """The guidance weight of every row of an x0-form schedule, fp32 [K] (``itsd_set_guidance``'s w_rows). Row 0 is the
+    last step, row K - 1 the first (noisiest). ``spec`` is a kind name or a dict with ``kind`` and that kind's keys:
+
+    * ``constant``: w on every row;
+    * ``interval`` (``t_lo``, ``t_hi``): w where t_lo <= tau[k] <= t_hi (both edges included), else 0 -- limited-interval
+      guidance; a 0 row runs the cond-only step;
+    * ``linear`` (``w_top``, ``w_end``): w_top at row K - 1 to w_end at row 0, linear in the row index (K = 1: w_end);
+    * ``table`` (``values``): K numbers, by row.
+
+    Values are formed in fp64 and cast once; every weight must be finite."""
+    tau = [int(t) for t in tau]
+    K = len(tau)
+    if K < 1:
+        raise ValueError("guidance: the schedule has no rows")
+    if isinstance(spec, str):
+        spec = {"kind": spec}
+    if not isinstance(spec, dict):
+        raise ValueError("guidance must be a kind name or a mapping with guidance.kind")
+    kind = spec.get("kind")
+    if kind not in GUIDANCE_KINDS:
+        raise ValueError(f"guidance.kind = {kind!r} must be one of {GUIDANCE_KINDS}")
+    keys = {"constant": (), "interval": ("t_lo", "t_hi"), "linear": ("w_top", "w_end"), "table": ("values",)}[kind]
+    for k in spec:
+        if k != "kind" and k not in keys:
+            raise ValueError(f"guidance.{k} does not belong to guidance.kind = {kind!r} (its keys: {keys})")
+    for k in keys:
+        if k not in spec:
+            raise ValueError(f"guidance.{k} is required by guidance.kind = {kind!r}")
+    w = _finite("w", w)
+    if kind == "constant":
+        v = [w] * K
+    elif kind == "interval":
+        lo, hi = spec["t_lo"], spec["t_hi"]
+        for name, t in (("t_lo", lo), ("t_hi", hi)):
+            if isinstance(t, bool) or not isinstance(t, int) or t < 0:
+                raise ValueError(f"guidance.{name} = {t!r} must be an integer timestep >= 0")
+        if hi < lo:
+            raise ValueError(f"guidance.t_hi = {hi} < guidance.t_lo = {lo}")
+        v = [w if lo <= t <= hi else 0.0 for t in tau]
+    elif kind == "linear":
+        top, end = _finite("guidance.w_top", spec["w_top"]), _finite("guidance.w_end", spec["w_end"])
+        v = [end + (top - end) * (k / (K - 1)) if K > 1 else end for k in range(K)]
+    else:
+        vals = spec["values"]
+        if not isinstance(vals, (list, tuple)) or len(vals) != K:
+            raise ValueError(f"guidance.values must list {K} numbers, one a row")
+        v = [_finite(f"guidance.values[{k}]", x) for k, x in enumerate(vals)]
+    return torch.tensor(v, dtype=torch.float64).float()

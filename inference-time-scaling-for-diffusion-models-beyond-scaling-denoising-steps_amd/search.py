@@ -30,6 +30,7 @@ Two layers:
 from __future__ import annotations
 
 import dataclasses
+import math
 from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
 
 import torch
@@ -237,7 +238,12 @@ class ReferenceNoise:
 class SearchEngine:
     """Batched, sharded search rounds over a sampler + native verifier."""
 
-    def __init__(self, sampler, verifier, seed: int = 0, group=None, graph: bool = True, noise: str = "philox"):
+    def __init__(self, sampler, verifier, seed: int = 0, group=None, graph: bool = True, noise: str = "philox",
+                 guidance_scales: Optional[Sequence[float]] = None):
+        """``guidance_scales``: per-candidate multipliers of the conditional sampler's guidance weight. Global
+        candidate g of every round runs with ``scales[g % len(scales)]`` on each of its images
+        (``sampler.run(.., guidance_scale=)``): a function of the global index, so the same on every rank. Random,
+        zero-order and placeholder path search only."""
         if not hasattr(verifier, "kind"):
             raise TypeError("SearchEngine needs an itsd verifier (OracleVerifier / SelfSupervisedVerifier / "
                             "AestheticPredictor / DenoisingVerifier); wrap custom scorers in the sequential API")
@@ -258,6 +264,12 @@ class SearchEngine:
         if noise == "reference" and getattr(sampler, "sampler", "ddpm") != "ddpm":
             raise ValueError("noise='reference' needs the ancestral sampler: the reference has no few-step draw order")
         self.noise = noise
+        self.guidance_scales: Optional[List[float]] = None
+        if guidance_scales is not None:
+            gs = [float(v) for v in guidance_scales]
+            if not gs or any(not math.isfinite(v) or v < 0.0 for v in gs):
+                raise ValueError("guidance_scales must be a non-empty list of finite numbers >= 0")
+            self.guidance_scales = gs
         self.verifier_unet_steps = 0  # UNet evaluations a model-as-verifier spent in the current search (_score)
         self.nfes = 0  # denoise calls (candidates), as search_algorithm.py:72 counts them
         self.device = sampler.model.device
@@ -284,6 +296,31 @@ class SearchEngine:
         if getattr(self.verifier, "needs_context", False):
             hist["verifier_unet_steps"] = self.verifier_unet_steps
         return hist
+
+    def candidate_scale(self, g: int) -> float:
+        """The guidance multiplier of global candidate g (1 without ``guidance_scales``)."""
+        gs = self.guidance_scales
+        return 1.0 if gs is None else gs[int(g) % len(gs)]
+
+    def _scale_kw(self, g0: int, nl: int, b: int) -> Dict[str, Any]:
+        """``sampler.run``'s guidance_scale for this rank's candidates g0..g0+nl-1 of b images each (nothing without
+        ``guidance_scales``: the call is then what it always was)."""
+        if self.guidance_scales is None:
+            return {}
+        v = [self.candidate_scale(g0 + j) for j in range(nl) for _ in range(b)]
+        return {"guidance_scale": torch.tensor(v, dtype=torch.float32)}
+
+    def _scales_hist(self, hist: Dict[str, Any], n: int, best_index: int) -> Dict[str, Any]:
+        """hist, plus the n candidates' multipliers and the best candidate's, under ``guidance_scales``."""
+        if self.guidance_scales is not None:
+            hist["guidance_scales"] = [self.candidate_scale(g) for g in range(n)]
+            hist["best_guidance_scale"] = self.candidate_scale(best_index) if best_index >= 0 else None
+        return hist
+
+    def _no_scales(self, what: str) -> None:
+        if self.guidance_scales is not None:
+            raise ValueError(f"{what} does not take guidance_scales: only random, zero-order and placeholder path "
+                             "search run per-candidate guidance")
 
     def reserve(self, n_candidates: int, noise_shape) -> None:
         """Size the native UNet for this rank's shard of a round up front (weights are packed
@@ -328,17 +365,17 @@ class SearchEngine:
             x_cpu, z_cpu = ReferenceNoise(self.sampler.T).round(kind, n, shape, pivot, scale)
             self._ref_pending = (x_cpu, z_cpu)
             x = x_cpu.to(self.device, copy=True).contiguous()  # x_cpu stays the drawn x_T
-            self.sampler.run(x, labels=lab, noise=z_cpu, graph=self.graph)
+            self.sampler.run(x, labels=lab, noise=z_cpu, graph=self.graph, **self._scale_kw(g0, nl, shape[0]))
         else:
             x = self.candidate_noise(round_id, g0, nl, shape, pivot, scale)
-            self._denoise(round_id, x, g0, per, lab)
+            self._denoise(round_id, x, g0, per, lab, **self._scale_kw(g0, nl, shape[0]))
         return self._finish_round(x, n, nl, g0, lab)
 
-    def _denoise(self, round_id: int, x: torch.Tensor, g0: int, per: int, lab: Optional[torch.Tensor]) -> None:
+    def _denoise(self, round_id: int, x: torch.Tensor, g0: int, per: int, lab: Optional[torch.Tensor], **kw) -> None:
         """A Philox round's sampler run, in place on this rank's candidates x: keyed by (seed, round) and the
-        candidates' global element positions."""
+        candidates' global element positions. kw: ``_scale_kw``'s."""
         self.sampler.run(x, labels=lab, seed=(self.seed * 1000003 + round_id) & ((1 << 62) - 1),
-                         noise_offset=g0 * per, graph=self.graph)
+                         noise_offset=g0 * per, graph=self.graph, **kw)
 
     def _finish_round(self, x: torch.Tensor, n: int, nl: int, g0: int, lab: Optional[torch.Tensor]) -> RoundResult:
         """Score this rank's denoised candidates, gather the round's n scores, pick the winner."""
@@ -394,7 +431,8 @@ class SearchEngine:
             best_noise = self._noise_of(r, 0, noise_shape)
             self._keep_best_image(r, noise_shape)
         self._publish_best_image(noise_shape)
-        return best_noise, r.best_score, self._hist({"scores": r.scores.tolist(), "best_index": r.best_index})
+        hist = self._hist({"scores": r.scores.tolist(), "best_index": r.best_index})
+        return best_noise, r.best_score, self._scales_hist(hist, n_candidates, r.best_index)
 
     def zero_order_search(self, initial_noise: torch.Tensor, n_neighbors: int, lambda_radius: float,
                           n_iterations: int, labels=None):
@@ -404,6 +442,7 @@ class SearchEngine:
         pivot = initial_noise.to(self.device, torch.float32).contiguous()
         best_noise, best_score = pivot.clone(), float("-inf")
         hist = {"scores": [], "candidates_per_iter": [], "best_index": []}
+        best_cand = -1  # the best candidate's index in its round (every round deals the same multipliers)
         for it in range(n_iterations):
             r = self.run_round(1 + it, n_neighbors, shape, pivot=pivot, scale=1 - lambda_radius, labels=labels,
                                kind="zero_order")
@@ -414,9 +453,10 @@ class SearchEngine:
                 best_score = r.best_score
                 cand = self._noise_of(r, 1 + it, shape, pivot=pivot, scale=1 - lambda_radius)
                 best_noise, pivot = cand.clone(), cand.clone()
+                best_cand = r.best_index
                 self._keep_best_image(r, shape)
         self._publish_best_image(shape)
-        return best_noise, best_score, self._hist(hist)
+        return best_noise, best_score, self._scales_hist(self._hist(hist), n_neighbors, best_cand)
 
     def path_search(self, initial_noise: torch.Tensor, n_paths: int, noise_scale: float, injection_step: int = 400,
                     labels=None):
@@ -430,9 +470,9 @@ class SearchEngine:
             best = self._noise_of(r, 0, shape, pivot=pivot, scale=noise_scale)
             self._keep_best_image(r, shape)
         self._publish_best_image(shape)
-        return best, r.best_score, self._hist({"scores": r.scores.tolist(),
-                                               "injection_points": [injection_step] * n_paths,
-                                               "best_index": r.best_index})
+        hist = self._hist({"scores": r.scores.tolist(), "injection_points": [injection_step] * n_paths,
+                           "best_index": r.best_index})
+        return best, r.best_score, self._scales_hist(hist, n_paths, r.best_index)
 
     # --- gradient search without autograd: an antithetic ES estimate of the score's gradient, stepped by Adam
     def es_candidates(self, round_id: int, g0: int, count: int, shape, pivot: torch.Tensor,
@@ -466,6 +506,7 @@ class SearchEngine:
 
         Returns (best_noise, best_score, hist); hist: ``scores`` [it][N], ``grad_norms`` (|g|_2), ``best_index``,
         ``candidates_per_iter``, ``pivot_rms`` (sqrt(mean theta^2) after each step: the drift off the unit shell)."""
+        self._no_scales("gradient_search")
         n_pairs = int(n_pairs)
         if n_pairs < 1:
             raise ValueError("n_pairs must be >= 1")
@@ -551,6 +592,7 @@ class SearchEngine:
         ``unet_steps`` = N x (sampler steps run + one x_0 evaluation per stage), a guided pair counting once."""
         # rows of the sampler's schedule: timesteps for the ancestral sampler, the K rows of a few-step one (injection
         # and re-noising steps are then rows, and abar is indexed by row)
+        self._no_scales("path_search_branch")
         T = int(getattr(self.sampler, "n_steps", self.sampler.T))
         steps = [int(s) for s in injection_steps] if isinstance(injection_steps, (list, tuple)) else None
         if not steps or any(int(s) != s for s in injection_steps):
@@ -639,6 +681,7 @@ class SearchEngine:
         costs an evaluation."""
         from .verifier import moment_scores
 
+        self._no_scales("fk_search")
         kind = getattr(self.verifier, "trace_kind", None)
         if kind is None:
             raise ValueError("fk_search scores particles from the sampler's x_0 moments: the verifier needs a "

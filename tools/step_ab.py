@@ -12,6 +12,12 @@ the second untraced arm is the A/A spread the difference is read against.
 
 --samplers ddim,dpmpp2m times the second-order step against the x0-form step (--eta is ddim's; dpmpp2m is eta = 0); a
 kind may be listed twice (ddim,ddim) for the A/A spread of one step against itself.
+
+--guidance table (--arch c) times the ddim step guided from a constant guidance table (itsd_set_guidance: the x0-form
+tail's table-guided instantiation) against the same step guided by the schedule's scalar: arms scalar, table, scalar
+again, alternating in one process; the two scalar arms are the A/A spread. --guidance cond-only times the cond-only
+step (a table of zeros: the n conditional images alone) against the guided step (a constant table): arms guided,
+cond_only, guided again, and the ratio cond_only / guided.
 """
 import argparse
 import os
@@ -62,6 +68,39 @@ def trace_ab(args, smp, x, run_kw):
           f"({abs(best['untraced'] / best['untraced_again'] - 1) * 100:.3f} %)")
 
 
+def guidance_ab(args, make, x, run_kw):
+    """--guidance: ms/step of three arms, alternating, args.rounds times. Each arm is a sampler of its own on the one
+    handle (its warm run installs its schedule and table and captures its graphs before the timed run)."""
+    kw = dict(sampler="ddim", steps=1000, eta=args.eta, clip_x0=bool(args.clip_x0))
+    const, zeros = torch.full((1000,), 1.8), torch.zeros(1000)
+    if args.guidance == "table":
+        arms = [("scalar", make(**kw)), ("table", make(guidance=const, **kw)), ("scalar_again", make(**kw))]
+    else:
+        arms = [("guided", make(guidance=const, **kw)), ("cond_only", make(guidance=zeros, **kw)),
+                ("guided_again", make(guidance=const, **kw))]
+    res = {k: [] for k, _ in arms}
+    for r in range(args.rounds):
+        for name, smp in arms:
+            smp.run(x.clone(), t_begin=999, t_end=999 - 4, seed=1, **run_kw)  # capture + warm
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            smp.run(x.clone(), t_begin=999, t_end=999 - args.steps + 1, seed=1, **run_kw)
+            torch.cuda.synchronize()
+            ms = (time.perf_counter() - t0) * 1e3 / args.steps
+            res[name].append(ms)
+            want = args.steps if name == "cond_only" else 0
+            assert smp.last_cond_only_steps == want, f"{name}: {smp.last_cond_only_steps} cond-only steps"
+            print(f"round {r} {name}: {ms:.4f} ms/step", flush=True)
+    best = {k: min(v) for k, v in res.items()}
+    for k, v in res.items():
+        print(f"{k}: best {best[k]:.4f} median {sorted(v)[len(v) // 2]:.4f} ms/step")
+    (a, _), (b, _), (a2, _) = arms
+    base = min(best[a], best[a2])
+    print(f"{b} - {a} (best of each): {(best[b] - base) * 1e3:+.1f} us/step ({(best[b] / base - 1) * 100:+.3f} %), "
+          f"ratio {best[b] / base:.4f}; A/A spread of the two {a} arms: {abs(best[a] - best[a2]) * 1e3:.1f} us/step "
+          f"({abs(best[a] / best[a2] - 1) * 100:.3f} %)")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=32)
@@ -77,7 +116,13 @@ def main():
     ap.add_argument("--eta", type=float, default=1.0, help="ddim: eta (0: no draw at all)")
     ap.add_argument("--clip-x0", type=int, default=1, help="ddim: clip the x_0 estimate (0 | 1)")
     ap.add_argument("--trace", action="store_true", help="the traced against the untraced ddim step (and an A/A arm)")
+    ap.add_argument("--guidance", default="", help="table | cond-only (--arch c): the table-guided / the cond-only ddim "
+                                                    "step against the scalar / the guided one (and an A/A arm)")
     args = ap.parse_args()
+    if args.guidance:
+        if args.guidance not in ("table", "cond-only") or args.arch != "c":
+            raise SystemExit("--guidance table | cond-only needs --arch c (a guided model)")
+        args.samplers, args.variants = "ddim", "base"
     if args.trace:
         args.samplers, args.variants = "ddim", "base"
     if args.lib:
@@ -113,8 +158,11 @@ def main():
             raise SystemExit(f"--samplers: unknown kind {kind!r} (ddpm | ddim | dpmpp2m)")
         return make(sampler="ddim", steps=1000, eta=args.eta, clip_x0=bool(args.clip_x0))
 
-    smps = {k: sampler_of(k) for k in kinds}
     x = torch.randn(args.n, 3, args.img, args.img, device="cuda")
+    if args.guidance:
+        guidance_ab(args, make, x, run_kw)
+        return
+    smps = {k: sampler_of(k) for k in kinds}
     variants = [v if len(kinds) == 1 else f"{v}/{k}" for v in args.variants.split(",") for k in kinds]
     if args.trace:
         trace_ab(args, smps["ddim"], x, run_kw)
